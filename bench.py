@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py - MI355X measurements of the HairFastGAN hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 8] [--workload generator|swap256]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 8] [--workload generator|swap256] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the --steps steps and prints the headline line; nothing else runs.  --full adds
+everything else the line can carry (the extra objects below: per-kernel HIP events and rooflines, the exact-fp32 and
+fp16 comparison runs, the swap measurements, the CPU baselines; for swap256 also the check of the gathered images); the
+--no-* options trim a --full run.  --dump-outputs DIR writes what the timed path returned in its last step as float32
+.npy files (dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared file by file.
 
 --workload generator (default; BASELINE.json configs[1], the configuration the headline metric
   is quoted on): a "step" is one full StyleGAN2 1024^2 generator forward (range 0->8) of one batch
@@ -15,7 +21,7 @@
   per rank are ignored: the workload is the whole set; --warmup triples are run untimed first.
 
 Weights are the closed-form synthetic fill of oracle/synth.py (no checkpoints / network on the box);
-timing is weight-independent.  Prints ONE JSON line (rank 0).  Extra objects:
+timing is weight-independent.  Prints ONE JSON line (rank 0).  Extra objects (--full only):
   roofline      dominant MFMA kernel = the conv instantiation with the largest share of the timed
                 region (labels from hf_debug_last_path): ALGORITHMIC FLOPs of its launches / their
                 HIP-event durations, measured in this run on the launch stream.  peak: 157.3 TFLOP/s
@@ -72,6 +78,8 @@ GFLOP_PER_TRIPLE = 1545.0      # hot-path FLOPs of one swa
 GFLOP_POSTPROCESS = 774.0      # PostProcessModel (594 + 2 x 90 GFLOP)
 PMC_PROFILE = os.path.join("profiles", "pmc_traffic.json")
 PMC_PROFILE_SWAP = os.path.join("profiles", "pmc_traffic_swap.json")  # the batched swap pass (tools/make_pmc_traffic.py --between)
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+DUMP_SAMPLE = 1 << 22          # elements of the seeded sample of an output too large to write whole
 
 
 def emit(out):
@@ -85,6 +93,25 @@ def emit(out):
         pass
     sys.stdout.flush()
     print(json.dumps(out), flush=True)
+
+
+def dump_outputs(out_dir, name, t):
+    """--dump-outputs: the tensor `t` the timed path returned in its last step, as float32 .npy files under out_dir.
+    Written whole (<name>.npy) when it fits DUMP_MAX_BYTES; otherwise its first item whole (<name>_0.npy) and a fixed,
+    seeded sample of DUMP_SAMPLE elements of the whole tensor (<name>_sample.npy: flat indices drawn without replacement
+    by numpy's default_rng(0), ascending) - 29 MB for the 8 x 3 x 1024^2 images of the default run."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    t = t.detach()
+    if t.numel() * 4 <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.float().cpu().numpy())
+        return
+    np.save(os.path.join(out_dir, f"{name}_0.npy"), t[0].float().cpu().numpy())
+    idx = np.sort(np.random.default_rng(0).choice(t.numel(), size=DUMP_SAMPLE, replace=False))
+    flat = t.reshape(-1)
+    sample = flat[torch.from_numpy(idx).to(flat.device)]
+    np.save(os.path.join(out_dir, f"{name}_sample.npy"), sample.float().cpu().numpy())
 
 
 def summary_tail(out):
@@ -565,6 +592,13 @@ def main():
                          "also one pass per rank for 256 triples on 8 GPUs")
     ap.add_argument("--precision", choices=("f16x3", "f32", "f16"), default=None,
                     help="matrix-core mode of the 3x3 convs (default: HAIRFAST_CONV_PRECISION or f16x3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (per-kernel events and rooflines, comparison "
+                         "runs in other precisions, the swap measurements, CPU baselines, verification of gathered swap images); "
+                         "a plain run only sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step to DIR/<name>.npy (float32, "
+                         "at most 64 MB: a seeded sample of a larger output)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-exact-f32", action="store_true", help="skip the fp32-MFMA comparison run (profiling)")
     ap.add_argument("--no-kernel-events", action="store_true")
@@ -579,6 +613,8 @@ def main():
     ap.add_argument("--swap-triples", type=int, default=4,
                     help="generator workload: triples per GPU for the secondary hair-swap measurements (0 = skip)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         self_launch(args, sys.argv[1:])
@@ -640,7 +676,7 @@ def main():
             if args.swap_batch > 1:  # warm the batched shapes too (weight splits, plans)
                 hf.swap_batch([tuple(t.to(dev) for t in load(i)) for i in range(args.swap_batch)])
         barrier()
-        prof = None if args.no_kernel_events else []
+        prof = [] if args.full and not args.no_kernel_events else None
         _marshal.PROFILE = prof
         # hf_profile_marker_kernel dispatches bracket the timed region: tools/summarize_prof.py / make_pmc_traffic.py cut
         # rocprofv3's per-dispatch tables to it (warm-up and plan-time kernels - weight splits, conv_prepare - excluded)
@@ -655,7 +691,11 @@ def main():
         _runtime.lib().hf_profile_marker(2, _runtime.stream())
         _marshal.PROFILE = None
         assert images.shape == (args.triples, 3, 1024, 1024) and images.dtype == torch.uint8
-        verified = None if args.no_verify else verify_gathered(hf, images, load, dev, args.triples, rank, world, args.swap_batch)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, "images_u8", images)
+        verified = None
+        if args.full and not args.no_verify:
+            verified = verify_gathered(hf, images, load, dev, args.triples, rank, world, args.swap_batch)
         if rank == 0:
             out = {"metric": "hair_swap_triples_per_sec", "value": round(args.triples / elapsed, 3), "unit": "triples/s",
                    "n_gpus": world, "ranks_observed": ranks_observed, "steps": args.triples, "warmup": max(1, args.warmup),
@@ -675,7 +715,7 @@ def main():
                               "gather": "RCCL all_gather_into_tensor of uint8 images per 8 local triples (async)" if use_dist else "single process: no collective"},
                    "algorithmic_tflops_hot_path": round(args.triples * (GFLOP_PER_TRIPLE + GFLOP_POSTPROCESS) / elapsed / 1e3, 2),
                    "gflop_per_triple": GFLOP_PER_TRIPLE + GFLOP_POSTPROCESS,
-                   "balance": balance_report(st256, cpu_slice), "verified": verified}
+                   "balance": balance_report(st256, cpu_slice), "verified": verified, "full": bool(args.full)}
             if prof:
                 rep = kernel_report(prof, elapsed, precision, pmc=False)
                 attach_swap_pmc(rep, args.swap_batch, precision)
@@ -712,7 +752,7 @@ def main():
     if pending is not None:
         pending[1].wait()
     barrier()
-    prof = None if args.no_kernel_events else []
+    prof = [] if args.full and not args.no_kernel_events else None
     every = max(1, args.event_every)
     first_ev = min(every // 2, max(0, args.steps - 1))  # (not step 0: the host is still filling the stream there)
     n_bracketed = len(range(first_ev, args.steps, every))
@@ -724,7 +764,9 @@ def main():
         # per-kernel HIP events (the `roofline` durations) on every `every`-th step of the timed region: an event pair costs
         # ~8 us of serialised stream time, 41 pairs per forward = 0.3 ms - bracketing every step cost 6 % of the headline
         _marshal.PROFILE = prof if (prof is not None and i >= first_ev and (i - first_ev) % every == 0) else None
-        step()
+        img = step()
+        if i + 1 < args.steps:
+            img = None  # only the last step's images outlive their step (--dump-outputs)
     _marshal.PROFILE = None
     if pending is not None:
         pending[1].wait()
@@ -732,6 +774,9 @@ def main():
     elapsed = max_over_ranks(time.perf_counter() - t0)
     _runtime.lib().hf_profile_marker(2, _runtime.stream())
     overflow = _marshal.f16_overflow_count(_runtime.lib())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, "image", img)
+    img = None
 
     # comparison runs (outside the timed region): the same forward with every conv on the exact-fp32
     # MFMA, and BASELINE.json configs[4] (fp16 operands, batch 16)
@@ -754,7 +799,7 @@ def main():
             _runtime.set_conv_precision(prev)
 
     exact_f32 = f16_mode = None
-    if world == 1 and not args.no_exact_f32:
+    if world == 1 and args.full and not args.no_exact_f32:
         if precision != "f32":
             ev32 = None if args.no_kernel_events else []
             e32 = alt_run("f32", B, ev32)
@@ -780,7 +825,7 @@ def main():
     # sample: (a) the hot-path kernels of one swap replayed on resident tensors (eager / hipGraph),
     # (b) the complete HairFast.swap pipeline incl. H2D, the stages in between and the uint8 gather path.
     swap_info = pipeline_info = None
-    if args.swap_triples > 0:
+    if args.full and args.swap_triples > 0:
         swap_res = swap_schedule_bench(g, sd, dev, args.swap_triples)
         times = {m: (None if swap_res.get(m) is None else max_over_ranks(swap_res[m])) for m in ("eager", "hipgraph")}
         best = min((v for v in times.values() if v is not None), default=None)
@@ -807,7 +852,7 @@ def main():
                     hf.swap_batch([tuple(t.to(dev) for t in load(i)) for i in range(args.swap_batch)])
             barrier()
             # BASELINE.json configs[3] at its own size, strong-scaled: --pipeline-triples (default 256) triples of the WHOLE job,
-            # block-partitioned over the ranks - the driver's plain `bench.py --gpus N` yields the triples/s curve
+            # block-partitioned over the ranks - `bench.py --full --gpus N` yields the triples/s curve
             st_pipe = {}
             t0 = time.perf_counter()
             pipe_images, _ = parallel.swap_many(lambda a, b, c: hf.swap(a, b, c), n_pipe, load, device=dev, batch=args.swap_batch,
@@ -910,7 +955,8 @@ def main():
             "f16_split_clamped_elements": overflow,
             "timing_note": (f"the conv / streaming launches of every {every}th step of the timed region ({n_bracketed} of {args.steps} steps) "
                             "are bracketed by pairs of HIP events (the per-kernel durations of `roofline`); a bracketed step costs about "
-                            "0.3 ms more, which the headline includes (--no-kernel-events measures without any)") if prof else "no per-kernel events in the timed region",
+                            "0.3 ms more, which the headline includes (a run without --full, or with --no-kernel-events, has none)") if prof else "no per-kernel events in the timed region",
+            "full": bool(args.full),
             "priming_note": (f"{max(0, args.priming)} untimed forwards ran before the {args.warmup} warm-up steps: the first ~4 forwards of a process are "
                              "slower (plans, allocator growth, clocks: tools/probes/step_ramp.py, 97 / 5.1 / 4.8 / 4.6 / 4.5 ms); the timed region is "
                              "still exactly --steps forwards between two synchronisations"),
@@ -922,7 +968,7 @@ def main():
         if prof:
             out.update(kernel_report(prof, elapsed, precision, n_bracketed / args.steps))
         enc_states = pipeline_info.pop("_enc_states", None) if pipeline_info else None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sd)
             if enc_states is not None and "error" not in pipeline_info:  # the swap metric's own CPU figure
                 try:
@@ -937,7 +983,8 @@ def main():
             out["swap_schedule"] = swap_info
         if pipeline_info is not None:
             out["swap_pipeline"] = pipeline_info
-        out["summary"] = summary_tail(out)  # LAST key: a reader that only keeps the end of the line still sees the scalars that matter
+        if args.full:
+            out["summary"] = summary_tail(out)  # LAST key: a reader that only keeps the end of the line still sees the scalars that matter
         emit(out)
 
     if use_dist:

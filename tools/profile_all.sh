@@ -7,7 +7,7 @@
 #   tools/summarize_prof.py --between / tools/make_pmc_traffic.py --between (tools/finish_profiles.sh <tag>).
 tag=$1
 R=$GRAFT_REPO_ROOT
-B="python $R/bench.py --no-cpu-baseline --no-exact-f32 --swap-triples 0"
+B="python $R/bench.py --full --no-cpu-baseline --no-exact-f32 --swap-triples 0"
 cd /tmp && export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_${tag}_stats -o bench -- $B --steps 8 --warmup 2 > $R/gpurun_out/prof_${tag}_stats.log 2>&1
 echo "stats rc=$?"

@@ -7,7 +7,7 @@
 # Outputs under gpurun_out/prof_<tag>_*; summarise with tools/summarize_prof.py / tools/make_pmc_traffic.py.
 tag=$1
 R=$GRAFT_REPO_ROOT
-B="python $R/bench.py --no-cpu-baseline --no-exact-f32 --swap-triples 0"
+B="python $R/bench.py --full --no-cpu-baseline --no-exact-f32 --swap-triples 0"
 cd /tmp && export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_${tag}_stats -o bench -- $B --steps 3 --warmup 1 > $R/gpurun_out/prof_${tag}_stats.log 2>&1
 echo "stats rc=$?"
