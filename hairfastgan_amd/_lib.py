@@ -64,6 +64,10 @@ SIGNATURES = {
     "hf_pixel_norm_f32": [_f, _f, _i, _i, _st],
     "hf_bicubic_down_f32": [_f, _f, _f, _ll, _i, _i, _i, _st],
     "hf_dilate_erode_f32": [_f, _f, _f, _ll, _i, _i, _i, _st],
+    "hf_quantize_u8_f32": [_f, _f, _ll, _st],
+    "hf_poisson_setup_u8": [_f, _f, _f, _f, _f, _i, _i, _i, _i, _st],
+    "hf_poisson_jacobi_f32": [_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _st],
+    "hf_poisson_finish_u8": [_f, _f, _f, _f, _i, _i, _i, _i, _st],
     "hf_maxpool3x3s2_f32": [_f, _f, _ll, _i, _i, _st],
     "hf_gate_f32": [_f, _f, _f, _f, _f, _fl, _ll, _i, _st],
     "hf_upsample_nearest_f32": [_f, _f, _ll, _i, _i, _i, _i, _st],

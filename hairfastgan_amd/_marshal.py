@@ -1281,3 +1281,62 @@ def quick_gelu(lib, st, x):
     out = torch.empty_like(x)
     check(lib, lib.hf_quick_gelu_f32(_p(out), _p(x), x.numel(), st), "hf_quick_gelu_f32")
     return out
+
+
+# ---- Poisson image blending (csrc/poisson.h; hairfastgan_amd.image_utils chains these) ----
+POISSON_TBLOCKS = (1, 2, 4, 8, 16)  # the sweep depths hf_poisson_jacobi_f32 is instantiated for
+
+
+def _u8(t):
+    if t.dtype != torch.uint8:
+        raise TypeError(f"expected a uint8 tensor; got {t.dtype}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _poisson_dims(img, mask):
+    """img [N,C,H,W], mask [N,1,H,W] or [N,H,W] of the same N, H, W -> (N, C, H, W)."""
+    if img.ndim != 4 or mask.numel() != img.shape[0] * img.shape[2] * img.shape[3] or tuple(mask.shape[-2:]) != tuple(img.shape[-2:]):
+        raise ValueError(f"images must be [N,C,H,W] and the mask [N,1,H,W] of the same N, H, W; got {tuple(img.shape)}, {tuple(mask.shape)}")
+    return tuple(img.shape)
+
+
+def quantize_u8(lib, st, x):
+    """torchvision save_image's bytes of a float tensor (any shape): uint8(trunc(clamp(fl(fl(x*255) + 0.5), 0, 255)))."""
+    x = _c(x)
+    out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    check(lib, lib.hf_quantize_u8_f32(_p(out), _p(x), x.numel(), st), "hf_quantize_u8_f32")
+    return out
+
+
+def poisson_setup(lib, st, src, tgt, mask):
+    """u8 source / target [N,C,H,W] and mask [N,1,H,W] -> (B, X_0) fp32 [N,C,H,W] of the Jacobi solve."""
+    src, tgt, mask = _u8(src), _u8(tgt), _u8(mask)
+    n, c, h, w = _poisson_dims(tgt, mask)
+    if src.shape != tgt.shape:
+        raise ValueError(f"source {tuple(src.shape)} and target {tuple(tgt.shape)} differ in shape")
+    b = torch.empty(tgt.shape, dtype=torch.float32, device=tgt.device)
+    x0 = torch.empty_like(b)
+    check(lib, lib.hf_poisson_setup_u8(_p(b), _p(x0), _p(src), _p(tgt), _p(mask), n, c, h, w, st), "hf_poisson_setup_u8")
+    return b, x0
+
+
+def poisson_jacobi_into(lib, st, x_out, x_in, b, mask, sweeps, tblock):
+    """`sweeps` (1..tblock) Jacobi sweeps x_in -> x_out in one launch blocked `tblock` sweeps deep."""
+    x_in, b, mask = _c(x_in), _c(b), _u8(mask)
+    n, c, h, w = _poisson_dims(b, mask)
+    if x_out.shape != b.shape or x_in.shape != b.shape or not x_out.is_contiguous() or x_out.dtype != torch.float32:
+        raise ValueError("x_in, x_out and b must be contiguous fp32 tensors of one shape")
+    check(lib, lib.hf_poisson_jacobi_f32(_p(x_out), _p(x_in), _p(b), _p(mask), n, c, h, w, sweeps, tblock, st),
+          "hf_poisson_jacobi_f32")
+    return x_out
+
+
+def poisson_finish(lib, st, x, tgt, mask):
+    """out = Omega ? uint8(trunc(clamp(X, 0, 255))) : target, u8 [N,C,H,W]."""
+    x, tgt, mask = _c(x), _u8(tgt), _u8(mask)
+    n, c, h, w = _poisson_dims(tgt, mask)
+    if x.shape != tgt.shape:
+        raise ValueError(f"X {tuple(x.shape)} and target {tuple(tgt.shape)} differ in shape")
+    out = torch.empty_like(tgt)
+    check(lib, lib.hf_poisson_finish_u8(_p(out), _p(x), _p(tgt), _p(mask), n, c, h, w, st), "hf_poisson_finish_u8")
+    return out

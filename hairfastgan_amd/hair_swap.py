@@ -909,6 +909,22 @@ class HairFast:
         with conv_precision_scope(self.conv_precision), batch_invariant_scope(self.batch_invariant):
             return run_guarded(run)
 
+    def poisson_image_blending(self, final_image, face_img, dilate_erosion=30, maxn=115):
+        """utils/image_utils.py:58-94 with this object's BiSeNet: pastes the non-hair region of `face_img` (the image forms
+        `swap` takes) back into `final_image` (what `swap` returns) by Poisson image editing -> (PIL result, PIL mask), RGB.
+        hairfastgan_amd.image_utils has the steps, the quirks kept and what is pinned."""
+        return self.poisson_image_blending_batch([final_image], [face_img], dilate_erosion, maxn)[0]
+
+    def poisson_image_blending_batch(self, final_images, face_imgs, dilate_erosion=30, maxn=115):
+        """`poisson_image_blending` for the list `swap_batch` returns and the triples' faces: one BiSeNet call and one solver
+        chain for all pairs -> list of (PIL result, PIL mask); each pair's bytes equal a call of its own."""
+        from .image_utils import poisson_image_blending_many
+
+        cache = {}
+        faces = [self._as_tensor(img, cache) for img in face_imgs]
+        with conv_precision_scope(self.conv_precision), batch_invariant_scope(self.batch_invariant):
+            return poisson_image_blending_many(final_images, faces, dilate_erosion, maxn, parsing=self.parsing)
+
 
 # ---------------------------------------------------------------------------------------------
 # replay harness of round 1 (kept: tests/test_gpu_schedule.py and the graph runner use it)

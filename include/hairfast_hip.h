@@ -533,6 +533,22 @@ int hf_bicubic_down_f32(float *out, const float *x, const float *k1d, long long 
 int hf_dilate_erode_f32(float *dilated, float *eroded, const float *mask, long long planes, int h, int w, int radius,
                         void *stream);
 
+/* ---- Poisson image blending (utils/image_utils.py:58-94: save_image + `fpie -g max`; csrc/poisson.h) ----
+ * torchvision save_image's byte of x (n elements): uint8(trunc(clamp(fl(fl(x*255) + 0.5), 0, 255))), two roundings. */
+int hf_quantize_u8_f32(unsigned char *out, const float *x, long long n, void *stream);
+/* src / tgt: u8 [images, channels, h, w]; mask: u8 [images, h, w].  Omega = mask >= 128 minus the image border.
+ * b = the right-hand side (mixed source / target gradients + the target on the boundary of Omega), x0 = tgt on Omega;
+ * both 0 off Omega.  fp32 [images, channels, h, w]. */
+int hf_poisson_setup_u8(float *b, float *x0, const unsigned char *src, const unsigned char *tgt, const unsigned char *mask,
+                        int images, int channels, int h, int w, void *stream);
+/* `sweeps` (1 <= sweeps <= tblock) synchronous Jacobi sweeps x_in -> x_out (distinct buffers) in one launch, the tiles
+ * blocked tblock sweeps deep in LDS; tblock in {1, 2, 4, 8, 16}.  Bit-identical to `sweeps` launches with tblock 1. */
+int hf_poisson_jacobi_f32(float *x_out, const float *x_in, const float *b, const unsigned char *mask, int images, int channels,
+                          int h, int w, int sweeps, int tblock, void *stream);
+/* out = Omega ? uint8(trunc(clamp(x, 0, 255))) : tgt */
+int hf_poisson_finish_u8(unsigned char *out, const float *x, const unsigned char *tgt, const unsigned char *mask, int images,
+                         int channels, int h, int w, void *stream);
+
 /* ---- PostProcessModel's latent branch (models/Encoders.py:13-32, 119-131) ----
  * F.layer_norm over the last `dim` elements of each of `rows` rows (biased variance, eps inside the sqrt):
  * gamma / beta [dim] = elementwise affine (both NULL: LayerNorm(elementwise_affine=False), :19), lrelu != 0
