@@ -3,14 +3,6 @@
 #pragma once
 #include "hf_common.h"
 
-#ifndef HF_STORE_OUT
-#ifdef HF_NT_STORES
-#define HF_STORE_OUT(p, v) __builtin_nontemporal_store((v), (p))
-#else
-#define HF_STORE_OUT(p, v) (*(p) = (v))
-#endif
-#endif
-
 namespace hf_detail {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -93,7 +85,6 @@ struct ConvParams {
   const float *a_next, *t_next;
   float blur_kx[4], blur_ky[4];  // convh.hip FUSE: flipped 1-D factors of the (rank-1) 4x4 blur kernel applied in the epilogue
   int rgb_slabs;               // convh.hip fused ToRGB: slabs of the raw tensor the caller allocated ([B][slabs*3][H][W])
-  int dma_early;               // convh.hip PRE: issue a stage's DMAs in its first tap-step (short K loops) instead of spread
   int n_tiles;                 // convh.hip: tiles over all families; a block walks blockIdx.x + k*gridDim.x
   TileGeom g[3];
 };
@@ -282,7 +273,7 @@ __device__ __forceinline__ void store_tile(const ConvParams &P, const TileGeom &
             v = apply_act(v, P.act, P.alpha, P.scale, slv[r]);
             if (P.residual && !P.residual_pre) v += P.residual[go.o + obofs + pofs];
           }
-          HF_STORE_OUT(&ob[pofs], v);
+          ob[pofs] = v;
         }
       }
     }
@@ -369,7 +360,7 @@ __device__ __forceinline__ void store_tile_rows_impl(const ConvParams &P, const 
           v = (v > 0.0f ? v : v * slv[k]) * sc;
           if (qgelu) v = v / (1.0f + expf(-1.702f * v));  // uniform branch (per launch)
           if (RES && !res_pre) v += rv[RES ? g : 0][r];
-          if (store32) HF_STORE_OUT(ob, v);
+          if (store32) *ob = v;
           vq[k] = v;
         }
 #ifdef HF_WANT_F16_SPLIT
@@ -505,7 +496,7 @@ int launch_conv_h(ConvParams &P, int nterms, bool up, const void *wt_hi, const v
 // HF_E_INVALID when the layer does not qualify
 int launch_conv_rows(ConvParams &P, int nterms, const void *wt_hi, const void *wt_lo, hipStream_t st);
 extern thread_local int g_h_blocks;           // hf_debug_set_persistent_blocks: resident blocks the convh.hip grid is sized for (0 = 256 CUs)
-extern thread_local int g_h_tune;             // hf_debug_set_tuning: bit 0 force early stage DMAs (convh.hip), bit 1 never the GEMM's 128-channel blocks (gemm_h.hip), ... (include/hairfast_hip.h)
+extern thread_local int g_h_tune;             // hf_debug_set_tuning: bit 1 never the GEMM's 128-channel blocks (gemm_h.hip), ... (include/hairfast_hip.h)
 extern int g_batch_invariant;                 // hf_set_batch_invariant (process-wide): plans (split-K counts, tile forms) from the per-sample shape only
 // The batch count every decision that changes a sample's BITS is made with - the K partition (split-K factor) and the kernel
 // family (fp32 split-K / tap-GEMM / tiled fp16-core kernels differ in summation order): the real one, or - in batch-invariant

@@ -36,47 +36,6 @@
 
 using namespace hf_detail;
 
-#define HF_H_BARRIER() hf_barrier_keep_young<0>()
-#ifndef HF_H_SPLIT_STORE16
-#define HF_H_SPLIT_STORE16 0  // fused upsampling epilogue: 1 = split output as ONE 16-byte store per lane (v_permlane32_swap of the half-waves) instead of two 8-byte stores; measured equal (587 vs 595 us on the 1024^2 layer): the epilogue is not store-bound
-#endif
-#ifndef HF_H_SPLIT_STORE_PAIR
-#define HF_H_SPLIT_STORE_PAIR 1  // fused upsampling epilogue: the half-waves trade their halves of the two pixels (2X, 2X+1) of a position (v_permlane32_swap), every lane then owns ONE whole 16-byte unit: a store instruction writes 1 KiB contiguous instead of every other 8 bytes of it (half the write requests, half the store instructions); 0 = two 8-byte stores per pixel (A/B builds)
-#endif
-#ifndef HF_H_SWAP_XY
-#define HF_H_SWAP_XY 1  // 0: always the (tile walkers, cout tiles) grid (A/B builds)
-#endif
-#ifndef HF_H_PINGPONG
-#define HF_H_PINGPONG 1  // 0: the one-phase K loop (side work of a tap-step, then its MFMAs, all eight waves in lock-step) for A/B builds
-#endif
-#ifndef HF_H_EPI_ABLATE
-#define HF_H_EPI_ABLATE 0  // timing experiments on the fused upsampling epilogue only (WRONG results): 1 no output stores, 2 no lo part (one conversion per element), 4 no cross-wave exchange (no LDS round trip, no barriers), 8 no vertical taps
-#endif
-#ifndef HF_H_PP_ROLES
-#define HF_H_PP_ROLES 0  // ping-pong K loop (measured neutral: fused layers 552-569 vs 592 us, 512->512 @64^2 425 vs 410, r06j - off): 1 = the half that idles FIRST in a stage (waves 4-7, phase A) issues ALL activation copies of the next stage (HBM / Infinity-Cache latency: they get the whole stage to land), the other half (phase B) only the weight copies (L2 hits); 0 = every wave issues its share of both in its idle phase (A/B builds)
-#endif
-#ifndef HF_H_LATE_TABLES
-#define HF_H_LATE_TABLES 0  // 1: the next image's epilogue tables loaded at the head of the tile into registers and written to LDS after its K loop, no barrier (measured neutral: 1706.7 vs 1707.0 img/s, r06al - off)
-#endif
-#ifndef HF_H_ILV
-#define HF_H_ILV 1  // ping-pong K loop: 1 = the LDS fragment reads of the NEXT tap are issued between the MFMAs of the current one (sched_group_barrier: one read behind each MFMA) instead of in front of them - in its turn on the pipe a wave is alone on its SIMD, nothing else covers the ~150 cycles the eight ds_read_b128 take to issue (profiles/r06af_trace_same_res_64ch.txt: step -> mfma 200 ticks per tap beside 500 of MFMAs)
-#endif
-#ifndef HF_H_PP_EARLY_BAR
-#define HF_H_PP_EARLY_BAR 0  // ping-pong K loop: 1 = a half passes the barrier its partner waits at BEFORE the MFMAs of its last tap (A/B builds)
-#endif
-#ifndef HF_H_PP_EARLY_X
-#define HF_H_PP_EARLY_X 0  // ping-pong K loop: activation copies of the next stage the FIRST half issues right after requesting its first fragments (under their LDS latency, after the end-of-stage barrier) instead of in its idle phase (A/B builds)
-#endif
-#ifndef HF_H_FETCH_ORDER
-#define HF_H_FETCH_ORDER 0  // 1 = a tap's fragment reads in the order its MFMAs consume them (a-hi, b-hi, b-lo, a-lo) instead of a-hi a-lo b-hi b-lo
-#endif
-#ifndef HF_H_PP_PREFETCH
-#define HF_H_PP_PREFETCH 1  // ping-pong K loop: the half that computes second fetches its first tap's fragments BEFORE the role-swap barrier (0 = after: A/B builds)
-#endif
-#ifndef HF_H_ABLATE
-#define HF_H_ABLATE 0  // timing experiments only: 1 no activation loads, 2 no epilogue stores, 4 no weight DMA, 8 no activation DMA
-#endif
-
 #ifdef HF_H_TRACE
 // kernel-development build only: wave-level timeline of block 0 (s_memtime at pipeline points)
 __device__ unsigned long long hf_trace_buf[8 * 512];
@@ -98,32 +57,18 @@ namespace {
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 constexpr int KH = 16;  // input channels per stage = K of one MFMA
 
-// Scheduling pattern of one tap-step (HF_H_ILV): NR times (one MFMA, one LDS read), then the remaining MFMAs
-#ifndef HF_H_ILV_MODE
-#define HF_H_ILV_MODE 1  // 1: (MFMA, read) x NR, MFMA x rest; 2: the reads behind the LAST NR MFMAs; 3: two reads behind each of the first NR / 2 MFMAs (A/B builds)
-#endif
+// Scheduling pattern of one tap-step of the ping-pong K loop: NR times (one MFMA, one LDS read), then the remaining MFMAs.
+// The LDS fragment reads of the NEXT tap are issued between the MFMAs of the current one instead of in front of them - in its
+// turn on the pipe a wave is alone on its SIMD, nothing else covers the ~150 cycles the eight ds_read_b128 take to issue
+// (profiles/r06af_trace_same_res_64ch.txt: step -> mfma 200 ticks per tap beside 500 of MFMAs)
 template <int NR, int NM>
 __device__ __forceinline__ void hf_interleave() {
-  if constexpr (HF_H_ILV_MODE == 2 && NM > NR) __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
-  if constexpr (HF_H_ILV_MODE == 3) {
 #pragma unroll
-    for (int k = 0; k < NR / 2; ++k) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-    }
-    if constexpr (NR & 1) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-    }
-    if constexpr (NM > (NR + 1) / 2) __builtin_amdgcn_sched_group_barrier(0x008, NM - (NR + 1) / 2, 0);
-  } else {
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
-    }
-    if constexpr (HF_H_ILV_MODE != 2 && NM > NR) __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
+  for (int k = 0; k < NR; ++k) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
+    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
   }
+  if constexpr (NM > NR) __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
 }
 
 // Halo pixels the LDS activation tile is sized for: PT-pixel tiles of 32..TWMAX-pixel rows, and
@@ -160,22 +105,16 @@ constexpr int halo_pixels_max() {
 // fragments exist per chunk; the taps are grouped by fragment - {0,1,3,4} {2,5} {6,7} {8} - and a fragment is
 // fetched from LDS once per group instead of once per tap (8*PG instead of 18*PG ds_read_b128 per chunk: with
 // 32-channel-wide wave tiles the fragment reads alone saturated the LDS port at the MFMA rate).
-#ifndef HF_H_TAP_NATURAL
-#define HF_H_TAP_NATURAL 0  // experiments: 1 = natural tap order for UP as well (one fragment fetch per tap)
-#endif
-template <bool UP_>
+template <bool UP>
 __host__ __device__ constexpr int tap_at(int i) {
-  constexpr bool UP = UP_ && !HF_H_TAP_NATURAL;
   return !UP ? i : (i == 2 ? 3 : i == 3 ? 4 : i == 4 ? 2 : i);  // 0 1 3 4 2 5 6 7 8
 }
-template <bool UP_>
+template <bool UP>
 __host__ __device__ constexpr int tap_group(int i) {  // index of the activation fragment of position i
-  constexpr bool UP = UP_ && !HF_H_TAP_NATURAL;
   return !UP ? i : (i < 4 ? 0 : i < 6 ? 1 : i < 8 ? 2 : 3);
 }
-template <bool UP_>
+template <bool UP>
 __host__ __device__ constexpr int group_first(int g) {  // first position of group g (9 = none)
-  constexpr bool UP = UP_ && !HF_H_TAP_NATURAL;
   return !UP ? g : (g == 0 ? 0 : g == 1 ? 4 : g == 2 ? 6 : g == 3 ? 8 : 9);
 }
 
@@ -200,17 +139,13 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
   constexpr int XSLOTS = (PG == 1) ? 4 : 6;
   constexpr int BUF_UNITS = (FUSE && NPART * (W_UNITS + X_UNITS) < NW * XSLOTS * 64) ? NW * XSLOTS * 64 : NPART * (W_UNITS + X_UNITS);
   constexpr int N_WPIECE = NPART * W_UNITS / 64;        // 1 KiB DMA pieces per stage
-  // PP: the ping-pong K loop (below); PPR: its copy roles - activations by waves NW/2.., weights by waves 0..NW/2-1
-  constexpr bool PP = PRE && NW == 8 && HF_H_PINGPONG;
-  constexpr bool PPR = PP && HF_H_PP_ROLES;
-  constexpr int WNW = PPR ? NW / 2 : NW;                // waves that issue weight copies
-  constexpr int XNT = PPR ? NT / 2 : NT;                // threads that issue activation copies
-  constexpr int ND = (N_WPIECE + WNW - 1) / WNW;        // per issuing wave
+  constexpr bool PP = PRE && NW == 8;                   // the ping-pong K loop (below)
+  constexpr int ND = (N_WPIECE + NW - 1) / NW;          // per wave
   // weight DMAs: all in the first three tap-steps when activations are staged through registers
   // (their loads must be issued first thing); one per tap-step when everything is DMA (PRE) -
   // spreading the arrivals over the chunk measured +1..3 %
   constexpr int DMA_PER_STEP = PRE ? 1 : (ND + 2) / 3;
-  constexpr int XE = (X_UNITS + XNT - 1) / XNT;         // (pixel, kgroup) items per issuing thread per stage
+  constexpr int XE = (X_UNITS + NT - 1) / NT;          // (pixel, kgroup) items per thread per stage
   static_assert(W_UNITS % 64 == 0, "weight part must be whole 1 KiB pieces");
   static_assert(!FUSE || (UP && CT_TILES == 1 && WAVES_CO == 1 && TWMAX == 32), "FUSE: 32 co x (PG*WAVES_PX rows of 32 positions)");
   static_assert(!FUSE || BUF_UNITS * 16 >= NW * XSLOTS * 64 * 16, "FUSE: the exchange of one channel quad must fit a stage buffer");
@@ -226,7 +161,6 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
   const int wave = tid >> 6;
   const int li = lane & 31;
   const int lh = lane >> 5;  // k group of the lane: input channels 8*lh .. 8*lh+7 of the stage
-  const int xtid = PPR ? tid - NT / 2 : tid;  // index among the threads that stage activations (negative: none)
   const int wave_co = (wave / WAVES_PX) * (32 * CT_TILES);
   const int wave_pg = (wave % WAVES_PX) * PG;
   // grid = (tile walkers, cout tiles), or - ConvParams::swap_xy - (cout tiles, tile walkers): blocks are dispatched x-fastest, so
@@ -294,10 +228,10 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
     const int wp = (1 << G.lg_tw) + HALO, xs = ((1 << G.lg_th) + HALO) * wp;
 #pragma unroll
     for (int e = 0; e < XE; ++e) {
-      const int i = xtid + e * XNT;
+      const int i = tid + e * NT;
       const int kg = i / NPIX, pix = i - kg * NPIX;
       src[e] = -2;
-      if (i >= 0 && i < X_UNITS && pix < xs) {
+      if (i < X_UNITS && pix < xs) {
         const int hy = pix / wp, hx = pix - hy * wp;
         const int ys = T.ty0 + hy - 1, xc = T.tx0 + hx - 1;
         src[e] = (ys >= 0 && ys < P.h && xc >= 0 && xc < P.w) ? ys * P.w + xc : -1;
@@ -333,42 +267,6 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
     }
   };
 
-  // Unmodulated / pre-split kernels (no s): the NEXT image's tables in two steps - the loads at the head of the tile into
-  // registers, the LDS writes after the tile's K loop (HF_H_LATE_TABLES).  With the strided walk a block of a 512^2 layer
-  // changes image on every second tile, one of a 256^2 layer on every tile; load_s at the tile head cost a block-wide barrier
-  // and the exposed latency of its global loads in wave 0 - 5.9 k of the 83 k cycles of a 64 -> 64 @512^2 tile
-  // (profiles/r06af_trace_same_res_64ch.txt).  No barrier is needed: the slot written after tile i's K loop was last read in
-  // tile i-1's epilogue, which every wave has left (it passed tile i's stage barriers); readers (tile i+1's epilogue) are
-  // behind tile i+1's stage barriers.  Same values, same bits.
-  constexpr bool LATE_TABLES = !MOD && HF_H_LATE_TABLES;
-  float pend_d = 1.0f, pend_b = 0.0f, pend_sn = 1.0f, pend_rs = 0.0f, pend_rw[3] = {0.0f, 0.0f, 0.0f};
-  bool pend = false;
-  auto load_tables_issue = [&](int b) {
-    if (tid < CT) {
-      pend_d = P.d ? P.d[(long long)b * P.d_bstride + co0 + tid] : 1.0f;
-      pend_b = P.bias ? P.bias[co0 + tid] : 0.0f;
-      pend_sn = ((!UP || FUSE) && P.oh && P.s_next) ? P.s_next[(long long)b * P.cout + co0 + tid] : 1.0f;
-      if (!UP && P.rgb_out) {
-        pend_rs = P.rgb_s[(long long)b * P.cout + co0 + tid];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) pend_rw[c] = P.rgb_w[(co0 + tid) * 3 + c];
-      }
-    }
-  };
-  auto load_tables_commit = [&](int slot) {
-    if (tid < CT) {
-      float *ep = ep_base + slot * 3 * CT;
-      ep[tid] = pend_d * w_unscale * ep_fold;
-      ep[CT + tid] = P.bias ? pend_b * ep_fold : 0.0f;
-      ep[2 * CT + tid] = pend_sn;
-      if (!UP && P.rgb_out) {
-        float *rw = rgbw_base + slot * 3 * CT;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) rw[c * CT + tid] = pend_rw[c] * pend_rs;
-      }
-    }
-  };
-
   // prefetch source (tile whose stage is being staged): items, image base, s
   int e_src[XE];
   const float *xb;
@@ -379,8 +277,8 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
   // weight stage of `chunk`: uniform base + per-lane byte offset ((tap*2+kg)*cout + co0 + col)*16
   const unsigned lds_addr0 = hf_lds_addr(lds);
   auto dma_piece = [&](int i, int chunk, int bufsel) {
-    const int pc = wave + i * WNW;
-    if (wave < WNW && pc < N_WPIECE && !(HF_H_ABLATE & 4)) {
+    const int pc = wave + i * NW;
+    if (wave < NW && pc < N_WPIECE) {  // (wave < NW always holds, but hipcc allocates registers differently without it)
       const int part = pc / (W_UNITS / 64), q = pc % (W_UNITS / 64);
       const int u = q * 64 + lane;            // unit inside the part: (tap*2 + kg)*CT + co
       const int row = u / CT, col = u % CT;   // row = tap*2 + kg
@@ -395,10 +293,8 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
   // the image are masked out of the DMA and zero-filled by the same lane
   const char *xh_b = nullptr, *xl_b = nullptr;  // image base of the pre-split tensors (uniform)
   auto dma_x = [&](int e, int chunk, int bufsel) {
-    const int i = xtid + e * XNT;
+    const int i = tid + e * NT;
     const int kg = i / NPIX;
-    if (HF_H_ABLATE & 8) return;  // timing experiments: no activation DMA
-    if (PPR && wave < NW / 2) return;  // (uniform per wave)
     const bool inside = e_src[e] >= 0;
     int off = inside ? (kg * iplane + e_src[e]) * 16 : 0;
     HF_OPAQUE_I32(off);
@@ -426,7 +322,7 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
     HF_OPAQUE_I32(off);  // addresses recomputed per chunk, not kept live as 8 hoisted 64-bit pairs
 #pragma unroll
     for (int k = 0; k < 8; ++k)
-      xr[e][k] = (HF_H_ABLATE & 1) ? 1.0f : *reinterpret_cast<const float *>(xc + (unsigned)((off + k * iplane) * 4));
+      xr[e][k] = *reinterpret_cast<const float *>(xc + (unsigned)((off + k * iplane) * 4));
   };
   auto convert_item = [&](int e, int chunk, half8 *buf) {
     if (e_src[e] == -2) return;
@@ -485,7 +381,7 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
 #pragma unroll
     for (int e = 0; e < XE; ++e) convert_item(e, 0, lds);
   }
-  HF_H_BARRIER();
+  hf_barrier_keep_young<0>();
 
   int trace_n = 0;  // HF_H_TRACE builds: events recorded by this wave
   (void)trace_n;
@@ -777,23 +673,19 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
       HF_TRACE_POINT(30);  // fused epilogue: horizontal pass of the quad done
       float4 *xq = reinterpret_cast<float4 *>(xch);  // [wave][6][64 lanes]
       float4 *mine = xq + (wv * XSLOTS) * 64 + lane;
-      if (!(HF_H_EPI_ABLATE & 4)) {
 #pragma unroll
-        for (int ph = 0; ph < 4; ++ph) mine[ph * 64] = make_float4(H[ph][0][0], H[ph][0][1], H[ph][0][2], H[ph][0][3]);
-        if (PG > 1) {
+      for (int ph = 0; ph < 4; ++ph) mine[ph * 64] = make_float4(H[ph][0][0], H[ph][0][1], H[ph][0][2], H[ph][0][3]);
+      if (PG > 1) {
 #pragma unroll
-          for (int pc = 0; pc < 2; ++pc)
-            mine[(4 + pc) * 64] = make_float4(H[2 + pc][PG - 1][0], H[2 + pc][PG - 1][1], H[2 + pc][PG - 1][2], H[2 + pc][PG - 1][3]);
-        }
+        for (int pc = 0; pc < 2; ++pc)
+          mine[(4 + pc) * 64] = make_float4(H[2 + pc][PG - 1][0], H[2 + pc][PG - 1][1], H[2 + pc][PG - 1][2], H[2 + pc][PG - 1][3]);
       }
       HF_TRACE_POINT(31);  // rows published, before the barrier
-      if (!(HF_H_EPI_ABLATE & 4)) hf_barrier_lds();
+      hf_barrier_lds();
       HF_TRACE_POINT(32);  // after the barrier
       const float4 *above = xq + (max(wv - 1, 0) * XSLOTS) * 64 + lane, *below = xq + (min(wv + 1, NW - 1) * XSLOTS) * 64 + lane;
       constexpr int ABOVE_P1 = (PG == 1) ? 2 : 4;  // slot of phase (1, pc) of the LAST row of the wave above
       const int c4 = 8 * q + 4 * lh_o;  // first of the lane's 4 channels (tile relative)
-      // the lane's 4 channels are one half (lh) of the 16-byte unit of channel block q
-      const long long cb_ofs = (long long)q * oplane * 16 + lh_o * 8;
 #pragma unroll
       for (int g = 0; g < PG; ++g) {
         const int rr = row0 + g, Y = Y0 + g;
@@ -802,16 +694,12 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
         for (int a = 0; a < 2; ++a) {
           typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
           typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-          u32x2 hq[2], lq[2];  // HF_H_SPLIT_STORE_PAIR: the split results of the pixels (2X, 2X+1), stored after the pc loop
+          u32x2 hq[2], lq[2];  // the split results of the pixels (2X, 2X+1), stored after the pc loop
           bool ovf_a = false;
 #pragma unroll
           for (int pc = 0; pc < 2; ++pc) {
             // the H rows 2Y+a-1 .. 2Y+a+2 of this column: (Y-1, 1), (Y, 0), (Y, 1), (Y+1, 0), (Y+1, 1)
             float hm1[4], h2[4], h3[4];
-            if (HF_H_EPI_ABLATE & 4) {
-#pragma unroll
-              for (int k = 0; k < 4; ++k) hm1[k] = H[pc][g][k], h2[k] = H[2 + pc][g][k], h3[k] = H[pc][g][k];
-            } else {
             if (g == 0 && a == 0) {
               const float4 u = above[(ABOVE_P1 + pc) * 64];
               hm1[0] = u.x; hm1[1] = u.y; hm1[2] = u.z; hm1[3] = u.w;
@@ -824,7 +712,6 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
                 h3[0] = d1.x; h3[1] = d1.y; h3[2] = d1.z; h3[3] = d1.w;
               }
             }
-            }
             const float4 dm = *reinterpret_cast<const float4 *>(ep + c4), bs = *reinterpret_cast<const float4 *>(ep + CT + c4);
             const float dmv[4] = {dm.x, dm.y, dm.z, dm.w}, bsv[4] = {bs.x, bs.y, bs.z, bs.w};
             float v[4];
@@ -834,9 +721,8 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
               const float h_0 = H[pc][g][k], h_1 = H[2 + pc][g][k];
               const float h_2 = (g == PG - 1) ? h2[k] : H[pc][g == PG - 1 ? g : g + 1][k];
               const float h_3 = (g == PG - 1) ? h3[k] : H[2 + pc][g == PG - 1 ? g : g + 1][k];
-              float o = (HF_H_EPI_ABLATE & 8) ? (a == 0 ? h_0 : h_1)
-                        : (a == 0) ? fmaf(kyf[3], h_2, fmaf(kyf[2], h_1, fmaf(kyf[1], h_0, kyf[0] * h_m1)))
-                                   : fmaf(kyf[3], h_3, fmaf(kyf[2], h_2, fmaf(kyf[1], h_1, kyf[0] * h_0)));
+              float o = (a == 0) ? fmaf(kyf[3], h_2, fmaf(kyf[2], h_1, fmaf(kyf[1], h_0, kyf[0] * h_m1)))
+                                 : fmaf(kyf[3], h_3, fmaf(kyf[2], h_2, fmaf(kyf[1], h_1, kyf[0] * h_0)));
               o = fmaf(o, dmv[k], fmaf(nw_f, nz[g][a * 2 + pc], bsv[k]));  // d and bias carry the output scale (ep_fold)
               v[k] = fmaxf(o, o * P.alpha);
             }
@@ -853,44 +739,13 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
               const float vs[4] = {v[0] * sn.x, v[1] * sn.y, v[2] * sn.z, v[3] * sn.w};
               hf_half4 h4, l4;
               bool ovf = false;
-              if (HF_H_EPI_ABLATE & 2) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) h4[k] = (_Float16)vs[k];
-                l4 = h4;
-              } else {
-                hf_split4_f16(vs, h4, l4, ovf);
-              }
-#if HF_H_SPLIT_STORE16
-              static_assert(NTERMS == 3, "HF_H_SPLIT_STORE16 pairs the hi and lo units of a pixel");
-              // one 16-byte store per lane: the half-waves trade halves, lanes 0-31 write the hi unit of the pixel,
-              // lanes 32-63 its lo unit (both halves of a wave share li, i.e. the pixel and its validity)
-              typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-              typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-              u32x2 hu = __builtin_bit_cast(u32x2, h4), lu = __builtin_bit_cast(u32x2, l4);
-              unsigned a0 = hu.x, b0 = lu.x, a1 = hu.y, b1 = lu.y;
-              hf_half_swap(a0, b0);
-              hf_half_swap(a1, b1);
-              if (pv) {
-                ovf_tile = ovf_tile || ovf;
-                u32x4 unit;
-                unit.x = a0; unit.y = a1; unit.z = b0; unit.w = b1;
-                *reinterpret_cast<u32x4 *>((lh_o ? ol_b : oh_b) + (long long)q * oplane * 16 + (long long)pix * 16) = unit;
-              }
-#elif HF_H_SPLIT_STORE_PAIR
+              hf_split4_f16(vs, h4, l4, ovf);
               hq[pc] = __builtin_bit_cast(u32x2, h4);
               lq[pc] = __builtin_bit_cast(u32x2, l4);
               ovf_a = ovf_a || ovf;
-#else
-              if (pv && !((HF_H_EPI_ABLATE & 1) && P.alpha != 77.0f)) {
-                ovf_tile = ovf_tile || ovf;
-                *reinterpret_cast<hf_half4 *>(oh_b + cb_ofs + (long long)pix * 16) = h4;
-                if (NTERMS == 3) *reinterpret_cast<hf_half4 *>(ol_b + cb_ofs + (long long)pix * 16) = l4;  // plain fp16 consumer: no lo part
-              }
-#endif
             }
             __builtin_amdgcn_sched_barrier(0);
           }
-#if HF_H_SPLIT_STORE_PAIR && !HF_H_SPLIT_STORE16
           if (SPLIT) {
             // lanes i / i+32 hold channels 0-3 / 4-7 of the same two pixels: after the swap the low half-wave owns the whole unit
             // of pixel 2X, the high half-wave that of pixel 2X+1 - (a0, a1) = channels 0-3, (b0, b1) = channels 4-7 in both
@@ -907,18 +762,17 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
               hf_half_swap(c1, d1);
               ul.x = c0; ul.y = c1; ul.z = d0; ul.w = d1;
             }
-            if (pv && !((HF_H_EPI_ABLATE & 1) && P.alpha != 77.0f)) {
+            if (pv) {
               ovf_tile = ovf_tile || ovf_a;
               *reinterpret_cast<u32x4 *>(oh_b + unit_ofs) = uh;
               if (NTERMS == 3) *reinterpret_cast<u32x4 *>(ol_b + unit_ofs) = ul;
             }
             __builtin_amdgcn_sched_barrier(0);
           }
-#endif
         }
       }
       HF_TRACE_POINT(33);  // vertical pass + tail + stores of the quad issued
-      if (!(HF_H_EPI_ABLATE & 4) || q == 3) hf_barrier_lds();  // everyone has read: the region may be overwritten (next quad / next tile's DMA)
+      hf_barrier_lds();  // everyone has read: the region may be overwritten (next quad / next tile's DMA)
       HF_TRACE_POINT(34);
     }
     hf_note_overflow(ovf_tile);
@@ -970,19 +824,12 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
     if (has_next) {
       nxt = locate(t_next);
       if (nxt.b0 != cur.b0) {
-        if constexpr (LATE_TABLES) {
-          sl_slot ^= 1;
-          nxt_sl_off = sl_slot * P.cin;
-          load_tables_issue(nxt.b0);
-          pend = true;
-        } else {
-          // the slot about to be overwritten held the image before this one: another wave may still
-          // be in that tile's epilogue (reading its d / bias) when images change on every tile
-          hf_barrier_lds();
-          sl_slot ^= 1;
-          nxt_sl_off = sl_slot * P.cin;
-          load_s(nxt.b0, sl_slot);
-        }
+        // the slot about to be overwritten held the image before this one: another wave may still
+        // be in that tile's epilogue (reading its d / bias) when images change on every tile
+        hf_barrier_lds();
+        sl_slot ^= 1;
+        nxt_sl_off = sl_slot * P.cin;
+        load_s(nxt.b0, sl_slot);
       }
     }
     HF_TRACE_POINT(8);  // next tile located
@@ -1027,30 +874,22 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
       // fragments of tap+1 are fetched from LDS while the MFMAs of tap run
       // UP with in-kernel staging: 128 accumulator registers + the staging registers leave no room
       // for a second fragment set
-#ifndef HF_H_DEEP_FETCH
-#define HF_H_DEEP_FETCH 0  // experiment: same-resolution kernels fetch the LDS fragments TWO taps ahead (three slots)
-#endif
-      constexpr int NSLOT = (UP && !PRE) ? 1 : ((!UP && HF_H_DEEP_FETCH) ? 3 : 2);
-      // PRE: all DMAs of the next stage in the first tap-step (short K loops: HBM latency exceeds the stage's MFMA
-      // time, the copies need the whole stage to land) or spread one per tap-step (long K loops, see DMA_PER_STEP)
-      const bool early = PRE && P.dma_early;
+      constexpr int NSLOT = (UP && !PRE) ? 1 : 2;
       half8 ah[NSLOT][CT_TILES], al[NSLOT][CT_TILES], bh[NSLOT][PG], bl[NSLOT][PG];
-      // part: 0 = hi and lo (program order hi0 lo0 hi1 lo1), 1 = hi only, 2 = lo only (HF_H_FETCH_ORDER: the reads in the order the
-      // MFMAs consume them - a-hi, b-hi, b-lo, a-lo)
-      auto fetch_a = [&](int slot, int tap, int part = 0) {
+      auto fetch_a = [&](int slot, int tap) {
 #pragma unroll
         for (int ct = 0; ct < CT_TILES; ++ct) {
-          if (part != 2) ah[slot][ct] = a_hi[tap * 2 * CT + ct * 32];
-          if (NTERMS == 3 && part != 1) al[slot][ct] = a_hi[OFF_WL + tap * 2 * CT + ct * 32];
+          ah[slot][ct] = a_hi[tap * 2 * CT + ct * 32];
+          if (NTERMS == 3) al[slot][ct] = a_hi[OFF_WL + tap * 2 * CT + ct * 32];
         }
       };
-      auto fetch_b = [&](int slot, int tap, int part = 0) {
+      auto fetch_b = [&](int slot, int tap) {
         const int ky = tap / 3, kx = tap % 3;
         const int brow = UP ? (ky == 2 ? 0 : 1) : ky, bcol = UP ? (kx == 2 ? 0 : 1) : kx;
 #pragma unroll
         for (int g = 0; g < PG; ++g) {
-          if (part != 2) bh[slot][g] = b_hi[pixrow[g][brow] + bcol];
-          if (NTERMS == 3 && part != 1) bl[slot][g] = b_hi[X_UNITS + pixrow[g][brow] + bcol];
+          bh[slot][g] = b_hi[pixrow[g][brow] + bcol];
+          if (NTERMS == 3) bl[slot][g] = b_hi[X_UNITS + pixrow[g][brow] + bcol];
         }
       };
       if (PP && pp_half == 1) {  // phase A of the second half: its copies of the next stage, then the role swap
@@ -1060,70 +899,40 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
 #pragma unroll
           for (int e = 0; e < XE; ++e) dma_x(e, cpf, cb ^ 1);
         }
-        if (HF_H_PP_PREFETCH) {  // the stage has been complete since the last end-of-stage barrier: the first tap's fragments
-                                 // travel while the other half still computes, not after the role swap
-          fetch_a(0, tap_at<UP>(0));
-          fetch_b(0, tap_at<UP>(0));
-        }
-        hf_barrier_lds();
-      }
-      if (!(PP && pp_half == 1 && HF_H_PP_PREFETCH)) {
+        // the stage has been complete since the last end-of-stage barrier: the first tap's fragments travel while the other
+        // half still computes, not after the role swap
         fetch_a(0, tap_at<UP>(0));
         fetch_b(0, tap_at<UP>(0));
-      }
-      if (PP && HF_H_PP_EARLY_X > 0 && pp_half == 0 && more1) {  // first half: some of its activation copies under the latency of its first fragments
-#pragma unroll
-        for (int e = 0; e < XE; ++e)
-          if (e < HF_H_PP_EARLY_X) dma_x(e, cpf, cb ^ 1);
-      }
-      if (NSLOT == 3) {
-        fetch_a(1, 1);
-        fetch_b(1, 1);
+        hf_barrier_lds();
+      } else {
+        fetch_a(0, tap_at<UP>(0));
+        fetch_b(0, tap_at<UP>(0));
       }
 #pragma unroll
       for (int i = 0; i < 9; ++i) {
         const int tap = tap_at<UP>(i);  // the side work below is scheduled by POSITION i
         HF_TRACE_POINT(10 + i);
         const int grp = tap_group<UP>(i);
-        const int sa = (NSLOT == 1) ? 0 : (NSLOT == 3 ? i % 3 : (i & 1)), sb = (NSLOT == 1) ? 0 : (NSLOT == 3 ? i % 3 : (grp & 1));
+        const int sa = (NSLOT == 1) ? 0 : (i & 1), sb = (NSLOT == 1) ? 0 : (grp & 1);
         if (NSLOT == 1) {
           if (i > 0) fetch_a(0, tap);
           if (i > 0 && group_first<UP>(grp) == i) fetch_b(0, tap);
-        } else if (NSLOT == 3) {  // !UP: natural tap order, one fragment pair per tap
-          if (i + 2 < 9) {
-            if (HF_H_FETCH_ORDER) {
-              fetch_a((i + 2) % 3, i + 2, 1);
-              fetch_b((i + 2) % 3, i + 2, 1);
-              fetch_b((i + 2) % 3, i + 2, 2);
-              fetch_a((i + 2) % 3, i + 2, 2);
-            } else {
-              fetch_a((i + 2) % 3, i + 2);
-              fetch_b((i + 2) % 3, i + 2);
-            }
-          }
         } else {
           const bool nb = group_first<UP>(grp) == i && group_first<UP>(grp + 1) < 9;
-          if (HF_H_FETCH_ORDER) {
-            if (i + 1 < 9) fetch_a(sa ^ 1, tap_at<UP>(i + 1), 1);
-            if (nb) fetch_b(sb ^ 1, tap_at<UP>(group_first<UP>(grp + 1)), 1);
-            if (nb) fetch_b(sb ^ 1, tap_at<UP>(group_first<UP>(grp + 1)), 2);
-            if (i + 1 < 9) fetch_a(sa ^ 1, tap_at<UP>(i + 1), 2);
-          } else {
-            if (i + 1 < 9) fetch_a(sa ^ 1, tap_at<UP>(i + 1));
-            // the next group's activation fragment, as soon as its slot is free (= when this group starts)
-            if (nb) fetch_b(sb ^ 1, tap_at<UP>(group_first<UP>(grp + 1)));
-          }
+          if (i + 1 < 9) fetch_a(sa ^ 1, tap_at<UP>(i + 1));
+          // the next group's activation fragment, as soon as its slot is free (= when this group starts)
+          if (nb) fetch_b(sb ^ 1, tap_at<UP>(group_first<UP>(grp + 1)));
         }
         // ---- side work of this step (PP: none - the copies are issued in the wave's other phase) ----
         if (!PP && more1) {
 #pragma unroll
           for (int j = 0; j < ND; ++j)
-            if ((early ? 0 : j / DMA_PER_STEP) == i) dma_piece(j, cpf, cb ^ 1);
+            if (j / DMA_PER_STEP == i) dma_piece(j, cpf, cb ^ 1);
         }
         if (!PP && PRE && more1) {  // activation DMAs in tap-steps 1, 3, 5, ...
 #pragma unroll
           for (int e = 0; e < XE; ++e)
-            if (i == (early ? 0 : ((2 * XE <= 9) ? 1 + 2 * e : 1 + e))) dma_x(e, cpf, cb ^ 1);
+            if (i == ((2 * XE <= 9) ? 1 + 2 * e : 1 + e)) dma_x(e, cpf, cb ^ 1);
         }
         if (!PRE && more1 && i == 0) {
 #pragma unroll
@@ -1134,16 +943,9 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
         if (more1 && i == 9 - XE) HF_TRACE_POINT(5);  // before the first conversion (waits for the loads)
         if (!PRE && more1 && i >= 9 - XE) convert_item(i - (9 - XE), cpf, nbuf);
         if (more1 && i == 8) HF_TRACE_POINT(6);  // conversions done
-        constexpr bool ILV = HF_H_ILV && PP && NSLOT >= 2;
+        constexpr bool ILV = PP && NSLOT >= 2;  // the next tap's fragment reads between this tap's MFMAs (hf_interleave)
         if (!ILV) __builtin_amdgcn_sched_barrier(0);
         HF_TRACE_POINT(20 + i);  // side work issued, before the MFMAs
-        if (PP && HF_H_PP_EARLY_BAR && i == 8) {
-          // the half's LAST tap: its fragments are in registers (the barriers wait for them), nothing of this stage is read from
-          // LDS any more - the barrier the other half waits at is passed BEFORE the tap's MFMAs instead of behind them: the other
-          // half's start-up (role swap: its first MFMAs; end of stage: the request of its first fragments) runs under them
-          if (pp_half == 0) hf_barrier_lds();
-          else HF_H_BARRIER();
-        }
         const int ph = UP ? (((tap / 3) & 1) * 2 + ((tap % 3) & 1)) : 0;
 #pragma unroll
         for (int ct = 0; ct < CT_TILES; ++ct)
@@ -1165,31 +967,24 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
         if constexpr (ILV) {
           constexpr int NRA = CT_TILES * (NTERMS == 3 ? 2 : 1), NRB = PG * (NTERMS == 3 ? 2 : 1), NM = CT_TILES * PG * NTERMS;
           const bool fb = group_first<UP>(grp) == i && group_first<UP>(grp + 1) < 9;  // this step fetched the next group's B fragments
-          if (NSLOT == 3) {
-            if (i + 2 < 9) hf_interleave<(NRA + NRB < NM ? NRA + NRB : NM), NM>();
-          } else if (i + 1 < 9 && fb) hf_interleave<(NRA + NRB < NM ? NRA + NRB : NM), NM>();
+          if (i + 1 < 9 && fb) hf_interleave<(NRA + NRB < NM ? NRA + NRB : NM), NM>();
           else if (i + 1 < 9) hf_interleave<(NRA < NM ? NRA : NM), NM>();
         }
         __builtin_amdgcn_sched_barrier(0);
       }
       HF_TRACE_POINT(2);  // chunk MFMAs issued, before the barrier
       if (PP && pp_half == 0) {  // phase B of the first half: role swap, then its copies of the next stage
-        if (!HF_H_PP_EARLY_BAR) hf_barrier_lds();
+        hf_barrier_lds();
         if (more1) {
 #pragma unroll
           for (int j = 0; j < ND; ++j) dma_piece(j, cpf, cb ^ 1);
 #pragma unroll
-          for (int e = 0; e < XE; ++e)
-            if (e >= HF_H_PP_EARLY_X) dma_x(e, cpf, cb ^ 1);
+          for (int e = 0; e < XE; ++e) dma_x(e, cpf, cb ^ 1);
         }
       }
       // next stage complete (DMA landed, conversions written), current one free
-      if (!(PP && HF_H_PP_EARLY_BAR && pp_half == 1)) HF_H_BARRIER();
+      hf_barrier_keep_young<0>();
       HF_TRACE_POINT(3);  // after the barrier
-    }
-    if (LATE_TABLES && pend) {  // the next image's tables: loaded at the head of this tile, they have long arrived
-      load_tables_commit(sl_slot);
-      pend = false;
     }
 
     if (FUSE) {
@@ -1316,7 +1111,6 @@ int launch_h(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, hipStream_
     return HF_E_INVALID;
   if (lds > 160 * 1024) return HF_E_INVALID;
   P.n_tiles = nblocks;
-  P.dma_early = (g_h_tune & 1) ? 1 : 0;  // measured (tools/probes/gen_layers.py): spread is 0-8 % faster on every generator layer
   // LDS allows one block per CU: size the grid to the chip and let each block walk its share
   // of the tiles as one pipeline (the tile-to-tile hand-over needs >= 2 stages per tile)
   const int co_tiles = P.cout / CT;
@@ -1333,7 +1127,7 @@ int launch_h(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, hipStream_
   // Block order (see csrc/convh_enc.hip launch_enc): tiles-fastest re-reads every input tile once per cout tile from beyond L2,
   // cout-tiles-fastest streams the weights once per group of resident input tiles instead - taken when that moves fewer bytes
   P.swap_xy = 0;
-  if (HF_H_SWAP_XY && co_tiles > 1 && gx <= 65535) {
+  if (co_tiles > 1 && gx <= 65535) {
     const double in_bytes = (double)P.batch * P.cin * P.h * P.w * 4.0, w_bytes = 9.0 * P.cin * P.cout * 4.0;
     const double tiles_fast = co_tiles * in_bytes + w_bytes;
     const double resident_tiles = co_tiles >= 256 ? 1.0 : 256.0 / co_tiles;

@@ -33,12 +33,10 @@
 
 using namespace hf_detail;
 
-#ifndef HF_ENC_ILV
-#define HF_ENC_ILV 1  // ping-pong K loop: the next tap's LDS fragment reads issued between the current tap's MFMAs (0: in front of them, A/B builds)
-#endif
 namespace {
 
-// Scheduling pattern of one tap-step (HF_ENC_ILV): NR times (one MFMA, one LDS read), then the remaining MFMAs
+// Scheduling pattern of one tap-step of the ping-pong K loop (the next tap's LDS fragment reads issued between the current
+// tap's MFMAs): NR times (one MFMA, one LDS read), then the remaining MFMAs
 template <int NR, int NM>
 __device__ __forceinline__ void hf_enc_interleave() {
 #pragma unroll
@@ -52,23 +50,8 @@ __device__ __forceinline__ void hf_enc_interleave() {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 constexpr int KH = 16;  // input channels per stage = K of one MFMA
-#ifndef HF_ENC_S2MT
-#define HF_ENC_S2MT 4  // pixel tiles per resident weight stage of the stride-2 multi-tile form (1 = off: A/B builds)
-#endif
-#ifndef HF_ENC_SWAP_XY
-#define HF_ENC_SWAP_XY 1  // 0: always the (tiles, columns) grid (A/B builds)
-#endif
-#ifndef HF_ENC_PINGPONG
-#define HF_ENC_PINGPONG 1  // 0: the one-phase K loop for every form (A/B builds: tools/build_variant.sh -DHF_ENC_PINGPONG=0)
-#endif
+constexpr int S2MT_MAX = 4;  // pixel tiles per resident weight stage of the stride-2 multi-tile form (at most)
 
-// 16-byte units of one activation part per kgroup that the LDS tile is sized for
-#ifndef HF_ENC_FAST_PROLOGUE
-#define HF_ENC_FAST_PROLOGUE 1
-#endif
-#ifndef HF_ENC_PERSIST
-#define HF_ENC_PERSIST 1
-#endif
 #ifdef HF_ENC_TRACE
 // kernel-development build only (tools/probes/trace_enc_layer.py): where a block of conv_enc_h spends its time - s_memtime stamps of
 // waves 0 and 7 in three blocks of the launch (the 1st, one of the 3rd round, one of a late round)
@@ -194,13 +177,13 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX) void conv_enc_h(const Con
       hf_glds16_raw_s(src, (unsigned)off, lds_addr0 + (unsigned)(bufsel * BUF_UNITS + part * W_UNITS + q * 64) * 16u);
     }
   };
-  // HF_ENC_FAST_PROLOGUE (round 5; tools/probes/trace_enc_layer.py: index arithmetic 2.4-3.3 k cycles, zero fill 1-1.5 k, first
+  // Fast prologue (round 5; tools/probes/trace_enc_layer.py: index arithmetic 2.4-3.3 k cycles, zero fill 1-1.5 k, first
   // stage 3-7.7 k - together 1.3 K stages per block, whatever the layer): the first stage's weights leave at once (they depend on
   // nothing below), its activations as soon as their addresses exist; only the halo units OUTSIDE the image are zeroed (by the
   // lanes that own them; the masked DMA never writes them) instead of both activation regions, and the divisions by the halo
   // pitch are divisions by its two possible values.
   const int c_first = (P.splits > 1 && !VSPLIT) ? (int)blockIdx.z * P.chunks_per_split : 0;
-  constexpr bool FASTP = PRE && HF_ENC_FAST_PROLOGUE;
+  constexpr bool FASTP = PRE;
   if (FASTP) {
 #pragma unroll
     for (int i = 0; i < ND; ++i) dma_piece(i, c_first, 0);
@@ -369,7 +352,7 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX) void conv_enc_h(const Con
   // the pipe idles while both waves of a SIMD sit in their DMA issues (100-185 cycles each, in-order waves: a tap-step took
   // 1.2-1.5 k cycles for 768 cycles of MFMA time, profiles/r04a_trace_fused.txt); here the partner's MFMAs cover them
   // (MI355X_MICROARCH.md, "Two waves per SIMD": matrix beside memory).  Same K order per wave: equal bits.
-  constexpr bool PP = PRE && NW == 8 && HF_ENC_PINGPONG;
+  constexpr bool PP = PRE && NW == 8;
   const int half = wave >> 2;  // PP: 0 computes in phase A, 1 in phase B
   half8 ah[2][CT_TILES], al[2][CT_TILES], bh[2][PG], bl[2][PG];
   auto compute_stage = [&](const half8 *buf) {  // the 9 taps of one K stage: fragments of tap+1 fetched under the MFMAs of tap
@@ -394,7 +377,6 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX) void conv_enc_h(const Con
     for (int tap = 0; tap < 9; ++tap) {
       const int s_ = tap & 1;
       if (tap + 1 < 9) fetch(s_ ^ 1, tap + 1);
-      if (!HF_ENC_ILV) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int ct = 0; ct < CT_TILES; ++ct)
 #pragma unroll
@@ -412,12 +394,10 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX) void conv_enc_h(const Con
           for (int g = 0; g < PG; ++g)
             acc[0][ct][g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[s_][ct], bh[s_][g], acc[0][ct][g], 0, 0, 0);
       }
-      if constexpr (HF_ENC_ILV != 0) {
-        // (round 6) the next tap's fragment reads BETWEEN this tap's MFMAs, one behind each: in its turn on the pipe the wave is
-        // alone on its SIMD - nothing else covers the time the reads take to issue (see HF_H_ILV, csrc/convh.hip)
-        constexpr int NRD = (CT_TILES + PG) * (NTERMS == 3 ? 2 : 1), NM = CT_TILES * PG * NTERMS;
-        if (tap + 1 < 9) hf_enc_interleave<(NRD < NM ? NRD : NM), NM>();
-      }
+      // (round 6) the next tap's fragment reads BETWEEN this tap's MFMAs, one behind each: in its turn on the pipe the wave is
+      // alone on its SIMD - nothing else covers the time the reads take to issue (see hf_interleave, csrc/convh.hip)
+      constexpr int NRD = (CT_TILES + PG) * (NTERMS == 3 ? 2 : 1), NM = CT_TILES * PG * NTERMS;
+      if (tap + 1 < 9) hf_enc_interleave<(NRD < NM ? NRD : NM), NM>();
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -564,9 +544,6 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX) void conv_enc_h(const Con
 // LDS-DMA meanwhile (two activation buffers by step parity, two weight buffers by chunk parity: the same 150 KB), one barrier per
 // step as before.  Bytes per MFMA: (38 + 36.9 / MT) KB per 216 instead of 75.  Per output the K order is that of conv_enc_h:
 // equal bits (tests/test_sim_encoders.py).  Pre-split input only; real split-K launches keep the one-tile form.
-#ifndef HF_ENC_S2MT_AREG
-#define HF_ENC_S2MT_AREG 1
-#endif
 template <int NTERMS, int MT, bool VSPLIT>
 __global__ __launch_bounds__(512) void conv_enc_s2mt_h(const ConvParams P, const _Float16 *__restrict__ wth_all,
                                                        const _Float16 *__restrict__ wtl_all) {
@@ -697,12 +674,12 @@ __global__ __launch_bounds__(512) void conv_enc_s2mt_h(const ConvParams P, const
   for (int e = 0; e < XE; ++e) dma_x(0, e, 0, 0);
   hf_barrier_keep_young<0>();
 
-  // HF_ENC_S2MT_AREG: the chunk's weight fragments (9 taps x hi / lo, 72 registers) are read from LDS during the chunk's first
+  // AREG: the chunk's weight fragments (9 taps x hi / lo, 72 registers) are read from LDS during the chunk's first
   // tile and stay in registers for its other MT - 1 tiles: 36 -> 18 ds_read_b128 per tile step for those (the 128-pixel form has
   // ONE accumulator tile per wave, 1.33 LDS reads per MFMA - twice the 512-pixel form's - and 8 waves' reads take longer than
   // their MFMAs)
   // (not with four tiles AND the virtual split-K's second accumulator set: 256 registers + scratch)
-  constexpr bool AREG = HF_ENC_S2MT_AREG && !(VSPLIT && MT == 4 && NTERMS == 3);
+  constexpr bool AREG = !(VSPLIT && MT == 4 && NTERMS == 3);
   half8 wh[AREG ? 9 : 2], wl[AREG ? 9 : 2], bh[2], bl[2];
   int step = 0;
   for (int c = 0; c < nchunks; ++c) {
@@ -789,15 +766,8 @@ __global__ __launch_bounds__(512) void conv_enc_s2mt_h(const ConvParams P, const
 //   T(s) = ceil(blocks * s / 256) * (3 + 0.9 * ceil(nchunks / s)) + (s > 1 ? 6 : 0),   s <= nchunks / 4, s <= 16
 // e.g. 96 blocks x 16 stages (256 -> 256 @ 32^2, batch 3): s = 2 (16.2; s = 1: 17.4, the old plan's s = 4 - 384 blocks, two rounds -
 // 19.2); 48 blocks x 32 stages (512 @ 16^2): s = 5; 192 blocks x 8 stages (128 @ 64^2): no split (the old plan: 2).
-// -DHF_ENC_PLAN_OLD: the round-2 rule (>= 1.5 blocks per CU) for A/B builds.
 inline int enc_splitk_plan(long long blocks, int nchunks) {
   if (blocks >= 256 || nchunks < 8) return 1;
-#ifdef HF_ENC_PLAN_OLD
-  int s = (int)((384 + blocks - 1) / blocks);
-  if (s > nchunks / 4) s = nchunks / 4;
-  if (s > 16) s = 16;
-  return s < 2 ? 1 : s;
-#else
   int best = 1;
   double best_t = 1e30;
   const int smax = nchunks / 4 < 16 ? nchunks / 4 : 16;
@@ -810,7 +780,6 @@ inline int enc_splitk_plan(long long blocks, int nchunks) {
     }
   }
   return best;
-#endif
 }
 
 // force_splits > 0 (batch-invariant plans): the K partition is given - the canonical plan of run_enc - and only its
@@ -860,7 +829,7 @@ int launch_enc(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, float *w
   // re-reads the weights once per such group (weights fit the 256 MB Infinity Cache; the input of a batched pass does not).
   // Taken when it moves fewer bytes from beyond L2 and no counters are keyed by (x, y) (real split-K keeps tiles-fastest).
   P.swap_xy = 0;
-  if (HF_ENC_SWAP_XY && (P.vsplit || P.splits == 1) && grid.x <= 65535 && grid.y > 1) {
+  if ((P.vsplit || P.splits == 1) && grid.x <= 65535 && grid.y > 1) {
     const double col_in = (double)P.batch * P.cin * P.h * P.w * 4.0;   // input bytes one column reads (hi + lo, or fp32)
     const double in_bytes = col_in * (P.x_gstride ? groups : 1);       // all inputs once
     const double w_bytes = 9.0 * P.cin * P.cout * 4.0 * groups;        // all weights once (hi + lo)
@@ -888,7 +857,7 @@ int launch_enc(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, float *w
   }
   g_s2mt_last = 0;
   if (P.xh) {
-    if constexpr (STRIDE == 2 && HF_ENC_S2MT > 1) {
+    if constexpr (STRIDE == 2) {
       // several pixel tiles per resident weight stage (conv_enc_s2mt_h) when the launch still fills the chip with MT times
       // fewer blocks (hf_debug_set_tuning bits 24-31 lower "the chip" for tests) and its K loop is not spread over the grid
       // MT = 4, else 2: the largest one whose blocks still fill the chip's rounds of 256 resident blocks (512 @ 32^2 at batch 96:
@@ -897,7 +866,7 @@ int launch_enc(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, float *w
       const int cols = P.co_tiles * groups, tiles = geom_blocks(G);
       int mt = 0;
       if (P.vsplit || P.splits == 1) {
-        for (int m = HF_ENC_S2MT; m >= 2 && !mt; m >>= 1) {
+        for (int m = S2MT_MAX; m >= 2 && !mt; m >>= 1) {
           const long long nb = (long long)hf_cdiv(tiles, m) * cols;
           const long long rounds = (nb + fill_blocks - 1) / fill_blocks;
           if (nb >= fill_blocks && (double)nb >= 0.85 * (double)(rounds * fill_blocks)) mt = m;
@@ -921,7 +890,7 @@ int launch_enc(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, float *w
   // persistent form: one resident block per CU walks the grid (forms whose LDS leaves room for one block per CU only)
   P.persist = 0;
   {
-    static const int on = [] { const char *e = getenv("HAIRFAST_ENC_PERSIST"); return e ? atoi(e) : HF_ENC_PERSIST; }();
+    static const int on = [] { const char *e = getenv("HAIRFAST_ENC_PERSIST"); return e ? atoi(e) : 1; }();
     const int resident = g_h_blocks > 0 ? g_h_blocks : 256;
     const bool ok = P.vsplit ? enc_persist_ok<NTERMS, CT_TILES, true>() : enc_persist_ok<NTERMS, CT_TILES, false>();
     if (on && ok && (P.vsplit || P.splits == 1) && lds > 80 * 1024 && blocks > resident) {

@@ -18,8 +18,8 @@
 //     of traffic at batch 8): the skip rows a super-step needs (6 rows x 34 columns x 3 channels) travel through a 16-row
 //     LDS ring like the input rows, two more 16-byte-per-lane copies per super-step.
 // Accumulation order per output value = the tiled kernel's (chunk, tap, hh / hl / lh): identical bits.
-// Measured at batch 8 (tools/probes/rows.py, bench.py): 732 -> 470 us per launch.  With the copies and the epilogue switched
-// off (hf_debug_set_tuning bits 5 / 6) the MFMA loop alone takes 340 us against 184 us of pure MFMA time at 2.4 GHz; the
+// Measured at batch 8 (bench.py): 732 -> 470 us per launch.  With the copies and the epilogue switched off (round-3 ablations,
+// DESIGN.md 4.9) the MFMA loop alone takes 340 us against 184 us of pure MFMA time at 2.4 GHz; the
 // copies add ~90 us and the epilogue ~60 us whether they are issued before the MFMA loop or between its MFMA groups, and
 // whether the two waves of a SIMD issue them together or apart - the phases do not overlap further at one block per CU.
 #include "conv_common.h"
@@ -30,12 +30,6 @@ namespace {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
-#ifndef HF_ROWS_PP
-#define HF_ROWS_PP 0  // 1 = ping-pong super-steps (measured SLOWER: 507 -> 559 us per launch, generator 0->8 -2.7 %, profiles/r06bn_*: the layer is bound by its row stream, not by epilogues beside an idle pipe - the two phases halve the time a step's copies have to land)
-#endif
-#ifndef HF_ROWS_ILV
-#define HF_ROWS_ILV HF_ROWS_PP  // (with ping-pong a computing wave is alone on its SIMD: its fragment reads go between its MFMAs)
-#endif
 constexpr int kSW = 64;                      // output columns of a strip
 constexpr int kPXW = kSW + 2;                // staged columns (x0 - 1 .. x0 + 64)
 constexpr int kPartUnits = 4 * kPXW;         // 16-byte units of one part (hi or lo) of a row slot: [channel block 4][66]
@@ -55,8 +49,7 @@ constexpr int kSkFloats = 4 * kSkGroup + 16 + 4;
 // MFMA per (tap, row) instead of three
 template <int NTERMS>
 __global__ __launch_bounds__(512, 2) void conv_rows_h(const ConvParams P, const _Float16 *__restrict__ wth,
-                                                      const _Float16 *__restrict__ wtl, int rows_per_block, int segs, int ablate) {
-  // ablate (hf_debug_set_tuning bits 5-7, timing experiments only): 1 no row copies, 2 no epilogue, 4 no MFMAs
+                                                      const _Float16 *__restrict__ wtl, int rows_per_block, int segs) {
   HF_DYN_LDS;
   half8 *ring = reinterpret_cast<half8 *>(hf_dyn_lds);                     // [kRing][kSlotUnits]
   float *ep = reinterpret_cast<float *>(ring + kRing * kSlotUnits);        // [32] d', [32] bias', [3][32] rgb weights
@@ -191,9 +184,8 @@ __global__ __launch_bounds__(512, 2) void conv_rows_h(const ConvParams P, const 
     for (int i = 0; i < 18; ++i) {
       const int c = i / 9, t = i % 9, sl = i & 1;
       if (i + 1 < 18) fetch(i + 1, sl ^ 1);
-      if (ablate & 4) continue;
-      if (dma && !(ablate & 1) && i < NPART * kDmaPerPart) dma_piece(i, y_next, slot_next);
-      if (!HF_ROWS_ILV) __builtin_amdgcn_sched_barrier(0);
+      if (dma && i < NPART * kDmaPerPart) dma_piece(i, y_next, slot_next);
+      __builtin_amdgcn_sched_barrier(0);
       acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[c][t], bh[sl][0], acc[0], 0, 0, 0);
       acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[c][t], bh[sl][1], acc[1], 0, 0, 0);
       if constexpr (NTERMS == 3) {
@@ -202,16 +194,6 @@ __global__ __launch_bounds__(512, 2) void conv_rows_h(const ConvParams P, const 
         acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[c][t], bh[sl][0], acc[0], 0, 0, 0);
         acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[c][t], bh[sl][1], acc[1], 0, 0, 0);
       }
-      if constexpr (HF_ROWS_ILV != 0) {  // the next tap's 2 (4) fragment reads between this tap's MFMAs (A/B: see HF_H_ILV, csrc/convh.hip)
-        if (i + 1 < 18) {
-#pragma unroll
-          for (int k = 0; k < 2 * NPART; ++k) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          }
-          __builtin_amdgcn_sched_group_barrier(0x008, (NTERMS == 3 ? 6 : 2) - 2 * NPART, 0);
-        }
-      }
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -219,7 +201,6 @@ __global__ __launch_bounds__(512, 2) void conv_rows_h(const ConvParams P, const 
   // scale is folded into d, bias and the noise weight, as in the tiled kernel's fast epilogue), fp32 output and / or the
   // fused ToRGB partial sums.  D layout: channel = (q & 3) + 8 * (q >> 2) + 4 * lh, pixel = li.
   auto epilogue = [&](const f32x16 &av, int ro, float noise_v) {
-    if (ablate & 2) return;
     int lh_o = lh;
     HF_OPAQUE_I32(lh_o);
     const int Y = r0 + ro;
@@ -299,39 +280,9 @@ __global__ __launch_bounds__(512, 2) void conv_rows_h(const ConvParams P, const 
       nz0 = np[0];
       nz1 = np[4LL * W];
     }
-    if constexpr (HF_ROWS_PP != 0) {
-      // Ping-pong (round 6, as the tiled kernels' K loops: csrc/convh.hip lesson 16): the two waves of a SIMD take TURNS on the
-      // matrix pipe.  Phase A: waves 0-3 run their 108 MFMAs alone on their SIMDs while waves 4-7 run the PREVIOUS step's
-      // epilogue and issue their row copies; role-swap barrier; phase B: waves 4-7 compute, waves 0-3 run THIS step's epilogue
-      // (their accumulators are complete) and issue their copies; end-of-step barrier (copies landed).  Every wave's epilogue
-      // falls into its idle phase - in the one-phase form all eight waves ran theirs side by side behind the barrier with the
-      // pipe idle (a step took ~2.3x its MFMA time).  Same arithmetic per wave: equal bits.
-      if (wave < 4) {
-        compute(ro, base18, false, y_next, slot_next);
-        hf_barrier_lds();
-        epilogue(acc[0], ro, nz0);
-        epilogue(acc[1], ro + 4, nz1);
-        if (more && !(ablate & 1)) dma_row(y_next, slot_next);
-        if (more && P.rgb_skip) dma_skip(sk_m + S + 1);
-      } else {
-        if (S > 0) {
-          epilogue(acc[0], ro - kStep, nzp[0]);
-          epilogue(acc[1], ro - kStep + 4, nzp[1]);
-        }
-        if (more && !(ablate & 1)) dma_row(y_next, slot_next);
-        hf_barrier_lds();
-        compute(ro, base18, false, y_next, slot_next);
-        nzp[0] = nz0;
-        nzp[1] = nz1;
-      }
-      hf_barrier_keep_young<0>();  // the new rows have landed, the oldest eight slots are free
-      base18 += kStep;
-      base18 = base18 >= kRing ? base18 - kRing : base18;
-      continue;
-    }
     // the two waves of a SIMD (w, w + 4) issue their copies at different times: one before its epilogue, the other between
     // the MFMA groups of its first ten taps - each stalls on the copy issue while its partner has MFMAs to issue
-    if (more && wave < 4 && !(ablate & 1)) dma_row(y_next, slot_next);
+    if (more && wave < 4) dma_row(y_next, slot_next);
     if (more && P.rgb_skip) dma_skip(sk_m + S + 1);  // the next super-step's new skip rows (waited for at this step's barrier)
     if (S > 0) {  // the previous super-step's epilogue: its stores drain under this step's MFMAs, none is waited for fresh
       epilogue(acc[0], ro - kStep, nzp[0]);
@@ -344,7 +295,7 @@ __global__ __launch_bounds__(512, 2) void conv_rows_h(const ConvParams P, const 
     base18 += kStep;
     base18 = base18 >= kRing ? base18 - kRing : base18;
   }
-  if (nsteps > 0 && !(HF_ROWS_PP != 0 && wave < 4)) {  // (ping-pong: waves 0-3 ran their last epilogue inside the loop)
+  if (nsteps > 0) {
     epilogue(acc[0], kStep * (nsteps - 1) + rw, nzp[0]);
     epilogue(acc[1], kStep * (nsteps - 1) + rw + 4, nzp[1]);
   }
@@ -385,10 +336,10 @@ int launch_conv_rows(ConvParams &P, int nterms, const void *wth, const void *wtl
   const size_t lds = (size_t)kRing * kSlotUnits * 16 + 5 * 32 * sizeof(float) + (P.rgb_skip ? kSkFloats * sizeof(float) : 0);
   if (nterms == 3)
     hipLaunchKernelGGL(conv_rows_h<3>, dim3((unsigned)blocks), dim3(512), lds, st, P, static_cast<const _Float16 *>(wth),
-                       static_cast<const _Float16 *>(wtl), rows_per_block, segs, (g_h_tune >> 5) & 7);
+                       static_cast<const _Float16 *>(wtl), rows_per_block, segs);
   else
     hipLaunchKernelGGL(conv_rows_h<1>, dim3((unsigned)blocks), dim3(512), lds, st, P, static_cast<const _Float16 *>(wth),
-                       static_cast<const _Float16 *>(wtl), rows_per_block, segs, (g_h_tune >> 5) & 7);
+                       static_cast<const _Float16 *>(wtl), rows_per_block, segs);
   return hf_launch_status();
 }
 

@@ -28,10 +28,7 @@ constexpr int KH = 16;   // input channels per MFMA k-step
 constexpr int KS = 32;   // input channels per LDS stage
 // Two blocks per CU: the 64 x 256 form's two stage buffers are exactly 80 KiB - half of a CU's 160 KiB - but without a register bound
 // hipcc spends 290 registers on it (one wave per SIMD, every LDS / DMA latency exposed); bounded to two waves per SIMD it needs
-// 226-240 and no scratch (round 5; -DHF_GEMM_MIN_WAVES=1 = the old build for A/B).
-#ifndef HF_GEMM_MIN_WAVES
-#define HF_GEMM_MIN_WAVES 2
-#endif
+// 226-240 and no scratch (round 5).
 // blocks from which a launch fills the chip without a K split (hf_debug_set_tuning bits 24-31 lower it for tests)
 inline int gemm_fill_blocks() { return ((hf_detail::g_h_tune >> 24) & 255) ? ((hf_detail::g_h_tune >> 24) & 255) : 256; }
 
@@ -44,7 +41,7 @@ inline int gemm_fill_blocks() { return ((hf_detail::g_h_tune >> 24) & 255) ? ((h
 // pixels, eight waves, one block per CU (96 KB): the activation stage (32 KB of the 40 a 64-channel block copies per 96 MFMAs) is
 // shared by twice the channels - 48 KB per 192 MFMAs, 250 instead of 427 bytes of LDS-DMA per MFMA.  Same K order: equal bits.
 template <int NTERMS, int PG, bool PRE, bool VSPLIT = false, int CW = 2>
-__global__ __launch_bounds__(128 * CW, HF_GEMM_MIN_WAVES) void gemm1x1_h(const ConvParams P, const _Float16 *__restrict__ wth_all,
+__global__ __launch_bounds__(128 * CW, 2) void gemm1x1_h(const ConvParams P, const _Float16 *__restrict__ wth_all,
                                                  const _Float16 *__restrict__ wtl_all) {
   constexpr int NW = 2 * CW, NT = 64 * NW, CT = 32 * CW, PT = 64 * PG;
   constexpr int NPART = (NTERMS == 3) ? 2 : 1;

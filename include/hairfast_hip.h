@@ -689,17 +689,16 @@ int hf_debug_last_path(void);
  * (0 = the MI355X's 256 CUs).  Tests use small values to exercise the tile hand-over.  Round 5: hf_conv2d_f16_f32's tile forms
  * that are alone on a CU walk their grid the same way (csrc/convh_enc.hip, ConvParams::persist) and size it by this count too. */
 int hf_debug_set_persistent_blocks(int blocks);
-/* Tuning switches of the fp16 matrix-core kernels (per thread, like the other debug hooks): bit 0 = issue every
- * stage's LDS-DMA copies in the stage's first tap-step instead of spreading them one per tap-step (the default,
- * measured 0-8 % faster on every generator layer); bit 1 = hf_conv1x1_f16_f32 never uses its 128-channel block form (round 6: eight
+/* Tuning switches of the fp16 matrix-core kernels (per thread, like the other debug hooks): bit 0 = ignored (it issued
+ * every stage's LDS-DMA copies in the stage's first tap-step: 0-8 % slower than spreading them, removed); bit 1 = hf_conv1x1_f16_f32 never uses its 128-channel block form (round 6: eight
  * waves sharing one activation stage - taken when the launch fills two rounds of CUs with it; a tile form: equal bits) and the
  * small-plane tap GEMM never trades its 256-pixel tiles for 128-pixel ones (taken when the last round of the 256-pixel form
  * would be under half full: three instead of two blocks per CU; equal bits);
  * bit 2 = hf_conv2d_f16_f32 never uses its 512-pixel tile form,
  * bits 8-15 = the minimum number of 512-pixel blocks / 8 for that form (0 = the default, 512), bits 16-23 = the
  * same for the 256-pixel form (default 384), bit 3 = the fp16-core conv kernels launch their grid columns-fastest whenever that is
- * legal (by default only when it moves fewer bytes from beyond L2; results do not depend on the block order; bits 5-7 are
- * timing ablations of the row-pipeline kernel), bits 24-31 = the block count from which a launch counts as filling the
+ * legal (by default only when it moves fewer bytes from beyond L2; results do not depend on the block order), bits 5-7 = ignored
+ * (timing ablations of the row-pipeline kernel, removed), bits 24-31 = the block count from which a launch counts as filling the
  * chip by itself (0 = the default, 256; batch-invariant plans: such a launch runs its K partition inside its blocks instead
  * of spreading it over the grid - tests reach that form on small shapes with it).  Results of the generator
  * kernels do not depend on it; tile forms of hf_conv2d_f16_f32 differ in summation order only. */

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Kernel-development build of the library with extra -D flags: hairfastgan_amd/csrc/libhairfast_<name>.so (git-ignored; load it
-# through HAIRFAST_HIP_LIB).  Usage: tools/build_variant.sh <name> [hipcc flags, e.g. -DHF_H_SPLIT_STORE16=0]
+# through HAIRFAST_HIP_LIB).  Usage: tools/build_variant.sh <name> [hipcc flags, e.g. -DHF_H_TRACE]
 set -e
 name=$1; shift
 cd "$(dirname "$0")/../hairfastgan_amd/csrc"

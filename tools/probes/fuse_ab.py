@@ -1,5 +1,6 @@
 """The three one-kernel upsampling StyledConv layers (pre-split input, split output, batch 8) timed under every library named on
-the command line (A/B builds of tools/build_one.sh / build_variant.sh): python fuse_ab.py hip var1 var2:32 ...  (name[:tuning bits] -> libhairfast_<name>.so under hf_debug_set_tuning).
+the command line (builds of the same ABI, e.g. the parent commit's library copied beside the current one): python fuse_ab.py hip base base:8 ...
+(name[:tuning bits] -> libhairfast_<name>.so under hf_debug_set_tuning).
 Each library runs in its own process (the library is bound at import)."""
 import os
 import subprocess

@@ -1,6 +1,5 @@
 """Per-layer timing of the generator's fast path at batch 8 (pre-split inputs): same-resolution convs (fp32 + split
-output / fused ToRGB), fused and two-pass upsampling convs - under the stage-DMA issue schedules of
-hf_debug_set_tuning (0 = library rule, 1 = early, 2 = spread)."""
+output / fused ToRGB), fused and two-pass upsampling convs."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -19,17 +18,11 @@ def timeit(fn, iters=10):
 dev = torch.device("cuda:0"); L, st = lib(), stream()
 k4 = O.blur_kernel_1d_to_2d(gain=4.0).to(dev); fac = M.blur_factors(k4)
 B = int(os.environ.get("PROBE_BATCH", "8"))
-modes = [int(m) for m in os.environ.get("PROBE_TUNE", "0,1,2").split(",")]
-print("layer".ljust(28) + " | " + " | ".join(f"tune {m}: us  TF/s" for m in modes))
+print("layer".ljust(28) + " |       us   TF/s")
 
 def report(name, flops, fn):
-    cells = []
-    for m in modes:
-        L.hf_debug_set_tuning(m)
-        t = timeit(fn)
-        cells.append(f"{t:8.1f} {flops / t * 1e-6:6.1f}")
-    L.hf_debug_set_tuning(0)
-    print(name.ljust(28) + " | " + " | ".join(cells), flush=True)
+    t = timeit(fn)
+    print(name.ljust(28) + f" | {t:8.1f} {flops / t * 1e-6:6.1f}", flush=True)
 
 for c, h, rgb in [(512, 64, False), (256, 128, False), (128, 256, False), (64, 512, True), (32, 1024, True)]:
     torch.manual_seed(0)

@@ -1,5 +1,6 @@
 """Timeline of block 0 (HF_H_TRACE build of csrc/convh.hip, loaded through HAIRFAST_HIP_LIB):
-python trace_layer.py cin cout res [batch] [mode]   mode: '' | pre | presplit (split output only) | prergb (fused ToRGB, no fp32 output) | up | uppre | fuse"""
+python trace_layer.py cin cout res [batch] [mode]   mode: '' | pre | presplit (split output only) | prergb (fused ToRGB, no fp32 output) | up | uppre | fuse
+Build: tools/build_variant.sh trace -DHF_H_TRACE -> hairfastgan_amd/csrc/libhairfast_trace.so (formerly tools/build_trace.sh)."""
 import ctypes, sys, os, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from hairfastgan_amd import _marshal as M

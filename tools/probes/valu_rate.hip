@@ -66,7 +66,7 @@ __global__ __launch_bounds__(512, 2) void kv(float *out, int iters, unsigned lon
 
 // Store shapes: every wave of the block issues bursts of 16 stores (as one channel quad of the epilogue), then waits (vmcnt 0).
 //   S=0: dwordx2, lane stride 32 B + 8 B for the upper half-wave (today: half of every 16-byte unit pair per instruction)
-//   S=1: dwordx4, lanes 0-31 at 32-byte stride, lanes 32-63 in a second array (round 4's HF_H_SPLIT_STORE16)
+//   S=1: dwordx4, lanes 0-31 at 32-byte stride, lanes 32-63 in a second array (round 4's one-store split output)
 //   S=2: dwordx4, 64 lanes contiguous (1 KiB per instruction)
 //   S=3: dwordx2, 64 lanes contiguous (512 B per instruction)
 template <int S>
