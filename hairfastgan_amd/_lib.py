@@ -18,7 +18,7 @@ _ll = ctypes.c_longlong
 _fl = ctypes.c_float
 _st = ctypes.c_void_p     # hipStream_t
 
-# name -> argtypes; every function returns int (0 == HF_OK) unless noted.
+# name -> argtypes of a function that returns int (0 == HF_OK), or (restype, argtypes).
 SIGNATURES = {
     "hf_upfirdn2d_f32": [_f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _st],
     "hf_fused_bias_act_f32": [_f, _f, _f, _ll, _i, _i, _fl, _fl, _st],
@@ -99,6 +99,15 @@ SIGNATURES = {
     "hf_profile_marker": [_i, _st],
     "hf_conv2d_f16_split_output_ok": [_i, _i, _i, _i, _i, _i, _i, _i],
     "hf_scale_shortcut_add_split_f16": [_f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _st],
+    "hf_strerror": (ctypes.c_char_p, [_i]),
+    "hf_abi_version": [],
+    "hf_modconv_workspace_floats": (_ll, [_i, _i, _i, _i, _i, _i]),
+    "hf_conv2d_workspace_floats": (_ll, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "hf_conv2d_f16_workspace_floats": (_ll, [_i, _i, _i, _i, _i, _i, _i]),
+    "hf_modconv3x3_small_workspace_floats": (_ll, [_i, _i, _i, _i, _i]),
+    "hf_conv1x1_f16_workspace_floats": (_ll, [_i, _i, _i, _i, _i, _i, _i]),
+    "hf_sample_layernorm_workspace_floats": (_ll, [_i, _i, _i]),
+    "hf_f16_overflow_count": (_ll, [_i]),
 }
 
 
@@ -108,31 +117,12 @@ class HairfastLibError(RuntimeError):
 
 def bind(cdll):
     """Attach argtypes/restype for every entry point of the ABI; raises if one is missing."""
-    for name, args in SIGNATURES.items():
+    for name, sig in SIGNATURES.items():
         try:
             fn = getattr(cdll, name)
         except AttributeError as e:
             raise HairfastLibError(f"{cdll._name}: missing symbol {name}") from e
-        fn.argtypes = args
-        fn.restype = ctypes.c_int
-    cdll.hf_strerror.argtypes = [ctypes.c_int]
-    cdll.hf_strerror.restype = ctypes.c_char_p
-    cdll.hf_modconv_workspace_floats.argtypes = [_i, _i, _i, _i, _i, _i]
-    cdll.hf_modconv_workspace_floats.restype = ctypes.c_longlong
-    cdll.hf_conv2d_workspace_floats.argtypes = [_i, _i, _i, _i, _i, _i, _i, _i]
-    cdll.hf_conv2d_workspace_floats.restype = ctypes.c_longlong
-    cdll.hf_conv2d_f16_workspace_floats.argtypes = [_i, _i, _i, _i, _i, _i, _i]
-    cdll.hf_conv2d_f16_workspace_floats.restype = ctypes.c_longlong
-    cdll.hf_modconv3x3_small_workspace_floats.argtypes = [_i, _i, _i, _i, _i]
-    cdll.hf_modconv3x3_small_workspace_floats.restype = ctypes.c_longlong
-    cdll.hf_conv1x1_f16_workspace_floats.argtypes = [_i, _i, _i, _i, _i, _i, _i]
-    cdll.hf_conv1x1_f16_workspace_floats.restype = ctypes.c_longlong
-    cdll.hf_sample_layernorm_workspace_floats.argtypes = [_i, _i, _i]
-    cdll.hf_sample_layernorm_workspace_floats.restype = ctypes.c_longlong
-    cdll.hf_f16_overflow_count.argtypes = [_i]
-    cdll.hf_f16_overflow_count.restype = ctypes.c_longlong
-    cdll.hf_abi_version.argtypes = []
-    cdll.hf_abi_version.restype = ctypes.c_int
+        fn.restype, fn.argtypes = sig if isinstance(sig, tuple) else (ctypes.c_int, sig)
     return cdll
 
 

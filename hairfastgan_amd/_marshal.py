@@ -15,7 +15,7 @@ import torch
 import torch.nn.functional as F
 
 from ._lib import check
-from ._runtime import plan_batch
+from ._runtime import CANON_BATCH, plan_batch
 
 SQRT2 = 2 ** 0.5
 
@@ -33,10 +33,11 @@ KERNEL_NAMES = {  # hf_debug_last_path() code -> kernel instantiation (csrc/modc
     224: "conv_mfma_pipe<1,2,2,4,up>", 225: "conv_mfma_pipe<1,1,1,4,up>", 300: "conv_mfma<1,1,2,2> split-K",
     # csrc/convh.hip (fp16 matrix cores; <CT_TILES,PG,WAVES_CO,WAVES_PX>)
     581: "conv_mfma_h<1,2,2,4,up,pre>", 583: "conv_mfma_h<1,2,1,8,up,pre>",
-    571: "conv_mfma_h<1,2,2,4,pre>", 572: "conv_mfma_h<2,2,1,8,pre>", 573: "conv_mfma_h<1,2,1,8,pre>", 575: "conv_mfma_h<1,2,1,8,tw128,pre>",
+    571: "conv_mfma_h<1,2,2,4,pre>", 572: "conv_mfma_h<2,2,1,8,pre>", 575: "conv_mfma_h<1,2,1,8,tw128,pre>",
     579: "conv_rows_h<32->32,strip64,pre>",
     551: "conv_mfma_h<1,2,2,4>", 552: "conv_mfma_h<2,2,1,8>", 553: "conv_mfma_h<1,2,1,8>", 555: "conv_mfma_h<1,2,1,8,tw128>",
     561: "conv_mfma_h<1,2,2,4,up>", 563: "conv_mfma_h<1,2,1,8,up>",
+    # (the library reports 573 for two forms: this one and "conv_mfma_h<1,2,1,8,pre>")
     573: "conv_mfma_h<1,2,1,8,up,fuse>", 593: "conv_mfma_h<1,2,1,8,up,pre,fuse>",
     # csrc/convh_enc.hip (encoder convs on the fp16 matrix cores)
     601: "conv_enc_h<64x256>", 602: "conv_enc_h<64x128,stride2>", 603: "conv_enc_h<64x128>", 604: "conv_enc_h<64x512>",
@@ -77,6 +78,27 @@ def _c(t):
     if t.dtype != torch.float32:
         raise TypeError(f"hairfastgan_amd kernels are fp32; got {t.dtype}")
     return t if t.is_contiguous() else t.contiguous()
+
+
+class SplitActivation:
+    """An activation handed from a producer to a 3x3 conv on the fp16 matrix cores without an fp32
+    round trip: s_next * y split into fp16 (hi, lo) and K-blocked [B, C/8, H, W, 8] (csrc/convh.hip)."""
+
+    def __init__(self, hi, lo, key):
+        self.hi, self.lo, self.key = hi, lo, key
+        b, cb, h, w, _ = hi.shape
+        self.shape = (b, cb * 8, h, w)
+
+    @classmethod
+    def empty(cls, b, c, h, w, device, want_lo=True, key=None):
+        """Uninitialised storage for a producer kernel to fill; want_lo=False: plain fp16 operands, no lo part."""
+        hi = torch.empty((b, c // 8, h, w, 8), dtype=torch.float16, device=device)
+        return cls(hi, torch.empty_like(hi) if want_lo else None, key)
+
+
+def _hl(split):
+    """(hi, lo) data pointers of a SplitActivation, (None, None) for None."""
+    return (None, None) if split is None else (_p(split.hi), _p(split.lo))
 
 
 def upfirdn2d(lib, st, x, kernel, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1):
@@ -276,10 +298,13 @@ def torgb_fusable(cin, cout, h, w):
     return h * w >= (512 if cout in (32, 64) else 4096)
 
 
+IMAGE_FUSE = os.environ.get("HAIRFAST_IMAGE_FUSE", "1") != "0"  # 0: the last layer as conv + ToRGB finishing pass (A/B, tests)
+
+
 def image_fusable(cin, cout, h, w):
     """The generator's last StyledConv whose epilogue finishes ToRGB (hf_modconv3x3_f16_pre_image_f32: the row pipeline's
     shapes).  The library may still decline (debug dispatch / tuning switches): modconv3x3_f16_pre_image then returns None."""
-    return cin == 32 and cout == 32 and w % 64 == 0 and h % 8 == 0 and os.environ.get("HAIRFAST_IMAGE_FUSE", "1") != "0"
+    return cin == 32 and cout == 32 and w % 64 == 0 and h % 8 == 0 and IMAGE_FUSE
 
 
 def modconv3x3_f16_pre_image(lib, st, act, wt_hi, wt_lo, nterms, d, noise, noise_w, bias, rgb, rgb_bias, skip, up_kernel,
@@ -352,14 +377,9 @@ def split_activation_reference(x, s):
     return blk(hi), blk(lo)
 
 
-def modconv3x3_f16_pre(lib, st, act, wt_hi, wt_lo, nterms, d, noise, noise_w, bias, alpha=0.2, scale=SQRT2, rgb=None,
-                       want_out=True, split_for=None):
-    """hf_modconv3x3_f16_pre_f32: same-resolution 3x3 conv on the fp16 matrix cores whose input is a
-    SplitActivation (modulation already applied by the producer).
-    rgb = (rgb_wt, rgb_s): fused ToRGB raw product (see modconv3x3_f16);
-    split_for = s_next [B,cout]: the epilogue also writes a SplitActivation of s_next*out for the next
-    layer's transposed conv; want_out=False: the fp32 activation itself is not written.
-    Returns out, or (out, raw), (out, split), (out, raw, split) in that order of optional parts."""
+def _modconv3x3_f16_pre(lib, st, act, wt_hi, wt_lo, nterms, d, noise, noise_w, bias, alpha=0.2, scale=SQRT2, rgb=None,
+                        want_out=True, split_for=None):
+    """modconv3x3_f16_pre with the fixed return form (out | None, raw | None, split | None)."""
     b, cin, h, w = act.shape
     cout = wt_hi.shape[3]
     dev = act.hi.device
@@ -368,14 +388,13 @@ def modconv3x3_f16_pre(lib, st, act, wt_hi, wt_lo, nterms, d, noise, noise_w, bi
         raise ValueError("want_out=False needs another consumer (rgb= or split_for=)")
     out = torch.empty((b, cout, h, w), dtype=torch.float32, device=dev) if want_out else None
     noise_w, bias = _c(noise_w), _c(bias)
-    raw = rgb_wt = rgb_s = sh = sl = s_next = None
+    raw = rgb_wt = rgb_s = split = s_next = None
     if rgb is not None:
         rgb_wt, rgb_s = _c(rgb[0]), _c(rgb[1])
         raw = torch.empty((b, 3 * torgb_slabs(cout), h, w), dtype=torch.float32, device=dev)
     if split_for is not None:
         s_next = _c(split_for)
-        sh = torch.empty((b, cout // 8, h, w, 8), dtype=torch.float16, device=dev)
-        sl = torch.empty_like(sh) if nterms == 3 else None  # plain fp16 consumer: no lo part
+        split = SplitActivation.empty(b, cout, h, w, dev, want_lo=nterms == 3)  # plain fp16 consumer: no lo part
     # algorithmic HBM bytes (bench.py: traffic / algorithmic): the split input once, every output form once, the weights once
     nparts = 2 if nterms == 3 else 1
     nb = (float(b) * h * w * (2.0 * nparts * cin + (4.0 * cout if want_out else 0.0) + (2.0 * nparts * cout if split_for is not None else 0.0)
@@ -384,14 +403,23 @@ def modconv3x3_f16_pre(lib, st, act, wt_hi, wt_lo, nterms, d, noise, noise_w, bi
         lib, 2.0 * cin * cout * 9 * h * w * b,
         lambda: lib.hf_modconv3x3_f16_pre_f32(_p(out), _p(act.hi), _p(act.lo), _p(wt_hi), _p(wt_lo), nterms, _p(d), _p(noise),
                                               _p(noise_w), nbs, _p(bias), b, cin, cout, h, w, alpha, scale, _p(raw),
-                                              _p(rgb_wt), _p(rgb_s), _p(sh), _p(sl), _p(s_next), st), nbytes=nb)
+                                              _p(rgb_wt), _p(rgb_s), *_hl(split), _p(s_next), st), nbytes=nb)
     check(lib, code, "hf_modconv3x3_f16_pre_f32")
-    res = [out]
-    if rgb is not None:
-        res.append(raw)
-    if split_for is not None:
-        res.append(SplitActivation(sh, sl, None))
-    return res[0] if len(res) == 1 else tuple(res)
+    return out, raw, split
+
+
+def modconv3x3_f16_pre(lib, st, act, wt_hi, wt_lo, nterms, d, noise, noise_w, bias, alpha=0.2, scale=SQRT2, rgb=None,
+                       want_out=True, split_for=None):
+    """hf_modconv3x3_f16_pre_f32: same-resolution 3x3 conv on the fp16 matrix cores whose input is a
+    SplitActivation (modulation already applied by the producer).
+    rgb = (rgb_wt, rgb_s): fused ToRGB raw product (see modconv3x3_f16);
+    split_for = s_next [B,cout]: the epilogue also writes a SplitActivation of s_next*out for the next
+    layer's transposed conv; want_out=False: the fp32 activation itself is not written.
+    Returns out, or (out, raw), (out, split), (out, raw, split) in that order of optional parts."""
+    out, raw, split = _modconv3x3_f16_pre(lib, st, act, wt_hi, wt_lo, nterms, d, noise, noise_w, bias, alpha, scale, rgb, want_out,
+                                          split_for)
+    res = (out,) + (() if rgb is None else (raw,)) + (() if split_for is None else (split,))
+    return res[0] if len(res) == 1 else res
 
 
 def split_weights_small(lib, st, wt):
@@ -414,9 +442,9 @@ def modconv3x3_small_supported(cin, cout, h, w, batch, upsample=False):
     if upsample:
         return h * w <= 64 or (h * w <= 256 and n <= 1024)
     # n = 256 from tiny planes (4^2 at batch 16, 8^2 at batch 4): the fp32 split-K kernel takes 180 us there, the tap GEMM 60
-    # 8^2 planes from n = 192 = the canonical batch 3 of the batch-invariant plans (round 6: at batch 8 the fp32 split-K family that
+    # 8^2 planes from n = CANON_BATCH * 64 = the canonical batch 3 of the batch-invariant plans (round 6: at batch 8 the fp32 split-K family that
     # batch 3 alone would take costs 53 us, the tap GEMM 29; at batch 3 itself 29 vs 31 - tools/probes/tower.py, profiles/r06an_*)
-    return 256 < n <= 2048 or (n == 256 and h * w <= 64) or (h * w == 64 and n >= 192 and n <= 2048)
+    return 256 < n <= 2048 or (n == 256 and h * w <= 64) or (h * w == 64 and CANON_BATCH * 64 <= n <= 2048)
 
 
 def conv3x3_small_supported(cin, cout, h, w, batch):
@@ -469,22 +497,21 @@ def modconv3x3_small_up_blur(lib, st, x, w9, nterms, s, d, blur_kernel, noise, n
     n = lib.hf_modconv3x3_small_workspace_floats(b, cin, cout, h, w)
     ws = x.new_empty((max(n, 1),))
     noise, nbs = _noise_args(noise, b, 4 * h * w)
-    out = sh = sl = s_next = key = None
+    out = split = s_next = None
     if split_for is not None:
-        key, s_next = split_for[0], _c(split_for[1])
-        want_lo = split_for[2] if len(split_for) > 2 else True
-        sh = torch.empty((b, cout // 8, 2 * h, 2 * w, 8), dtype=torch.float16, device=x.device)
-        sl = torch.empty_like(sh) if want_lo else None
+        s_next = _c(split_for[1])
+        split = SplitActivation.empty(b, cout, 2 * h, 2 * w, x.device, want_lo=split_for[2] if len(split_for) > 2 else True,
+                                      key=split_for[0])
     else:
         out = x.new_empty((b, cout, 2 * h, 2 * w))
     code = _launch_profiled(
         lib, 2.0 * cin * cout * 9 * h * w * b,
-        lambda: lib.hf_modconv3x3_small_up_blur_f16_f32(_p(out), _p(sh), _p(sl), _p(x), _p(hi), _p(lo), nterms, _p(_c(s)), _p(_c(d)),
+        lambda: lib.hf_modconv3x3_small_up_blur_f16_f32(_p(out), *_hl(split), _p(x), _p(hi), _p(lo), nterms, _p(_c(s)), _p(_c(d)),
                                                         _p(_c(blur_kernel)), _p(noise), _p(_c(noise_w)), nbs, _p(_c(bias)),
                                                         _p(s_next), b, cin, cout, h, w, alpha, scale, _p(ws), n, st),
         label="gemm_h tap-GEMM (small planes)")
     check(lib, code, "hf_modconv3x3_small_up_blur_f16_f32")
-    return out if split_for is None else SplitActivation(sh, sl, key)
+    return out if split_for is None else split
 
 
 def modconv3x3_up_f16_supported(cin, cout, h, w, batch=None):
@@ -493,16 +520,6 @@ def modconv3x3_up_f16_supported(cin, cout, h, w, batch=None):
     if batch is not None and plan_batch(batch) * h * w < 512:
         return False
     return cin % 16 == 0 and cout % 32 == 0 and h * w >= (256 if cout % 64 == 0 else 512) and min(h, w) >= 2
-
-
-class SplitActivation:
-    """An activation handed from a producer to a 3x3 conv on the fp16 matrix cores without an fp32
-    round trip: s_next * y split into fp16 (hi, lo) and K-blocked [B, C/8, H, W, 8] (csrc/convh.hip)."""
-
-    def __init__(self, hi, lo, key):
-        self.hi, self.lo, self.key = hi, lo, key
-        b, cb, h, w, _ = hi.shape
-        self.shape = (b, cb * 8, h, w)
 
 
 def modconv3x3_up(lib, st, x, wt, s, d, blur_kernel, noise, noise_w, bias, alpha=0.2, scale=SQRT2, f16=None,
@@ -518,23 +535,21 @@ def modconv3x3_up(lib, st, x, wt, s, d, blur_kernel, noise, noise_w, bias, alpha
     b, cin, h, w = x.shape
     cout = wt.shape[2]
     pitch = lib.hf_modconv_up_pitch(w)  # rows padded to a multiple of 4 floats (aligned 16 B loads in the blur)
-    if small is not None and not pre and SMALL_UP_FUSED and small_up_blur_supported(h, w):
-        # round 6: tap GEMM + ONE combine / blur / tail kernel (the (2h+1)^2 intermediate stays in LDS) - same bits
-        return modconv3x3_small_up_blur(lib, st, x, small[0], small[1], s, d, blur_kernel, noise, noise_w, bias, cout, alpha, scale,
-                                        split_for=split_for)
-    if small is not None and not pre:
-        tmp = modconv3x3_small(lib, st, x, small[0], small[1], s, d, None, None, None, cout, upsample=True)
-    else:
+    if pre or small is None:
         tmp = torch.empty((b, cout, 2 * h + 1, pitch), dtype=torch.float32, device=(x.hi if pre else x).device)
-    if small is not None and not pre:
-        pass
-    elif pre:  # pre-split input (modulation already applied by the producer): hf_modconv3x3_up_f16_pre_f32
+    if pre:  # pre-split input (modulation already applied by the producer): hf_modconv3x3_up_f16_pre_f32
         hi, lo, nterms = f16
         code = _launch_profiled(
             lib, 2.0 * cin * cout * 9 * h * w * b,
             lambda: lib.hf_modconv3x3_up_f16_pre_f32(_p(tmp), _p(x.hi), _p(x.lo), _p(hi), _p(lo), nterms, _p(d), b, cin, cout,
                                                      h, w, pitch, st))
         check(lib, code, "hf_modconv3x3_up_f16_pre_f32")
+    elif small is not None and SMALL_UP_FUSED and small_up_blur_supported(h, w):
+        # round 6: tap GEMM + ONE combine / blur / tail kernel (the (2h+1)^2 intermediate stays in LDS) - same bits
+        return modconv3x3_small_up_blur(lib, st, x, small[0], small[1], s, d, blur_kernel, noise, noise_w, bias, cout, alpha, scale,
+                                        split_for=split_for)
+    elif small is not None:
+        tmp = modconv3x3_small(lib, st, x, small[0], small[1], s, d, None, None, None, cout, upsample=True)
     elif f16 is not None:
         hi, lo, nterms = f16
         code = _launch_profiled(
@@ -551,20 +566,19 @@ def modconv3x3_up(lib, st, x, wt, s, d, blur_kernel, noise, noise_w, bias, alpha
         check(lib, code, "hf_modconv3x3_up_f32")
     noise, nbs = _noise_args(noise, b, 4 * h * w)
     if split_for is not None:
-        key, s_next = split_for[0], split_for[1]
+        s_next = split_for[1]
         want_lo = split_for[2] if len(split_for) > 2 else True  # False: consumer with plain fp16 operands
-        hi = torch.empty((b, cout // 8, 2 * h, 2 * w, 8), dtype=torch.float16, device=tmp.device)
-        lo = torch.empty_like(hi) if want_lo else None
+        split = SplitActivation.empty(b, cout, 2 * h, 2 * w, tmp.device, want_lo, key=split_for[0])
         # algorithmic bytes: the (2h+1)(2w+1) fp32 intermediate read once, one 2-byte value per part written
         nb = float(b * cout) * (4.0 * (2 * h + 1) * (2 * w + 1) + (4.0 if want_lo else 2.0) * 4 * h * w)
         code = _launch_profiled(
             lib, 0.0,
-            lambda: lib.hf_blur_noise_bias_act_split_f16(_p(hi), _p(lo), _p(tmp), _p(_c(blur_kernel)), _p(noise),
+            lambda: lib.hf_blur_noise_bias_act_split_f16(*_hl(split), _p(tmp), _p(_c(blur_kernel)), _p(noise),
                                                          _p(_c(noise_w)), nbs, _p(_c(bias)), _p(_c(s_next)), b, cout,
                                                          2 * h + 1, 2 * w + 1, pitch, alpha, scale, st),
             label="blur4x4_split8", nbytes=nb)
         check(lib, code, "hf_blur_noise_bias_act_split_f16")
-        return SplitActivation(hi, lo, key)
+        return split
     out = tmp.new_empty((b, cout, 2 * h, 2 * w))
     nb = float(b * cout) * 4.0 * ((2 * h + 1) * (2 * w + 1) + 4 * h * w)
     code = _launch_profiled(
@@ -609,24 +623,23 @@ def modconv3x3_up_fused(lib, st, x, wt_hi, wt_lo, s, d, factors, noise, noise_w,
     cout = wt_hi.shape[3]
     dev = x.hi.device if pre else x.device
     noise, nbs = _noise_args(noise, b, 4 * h * w)
-    out = sh = sl = s_next = None
+    out = split = s_next = None
     if split_for is not None:
         s_next = _c(split_for)
-        sh = torch.empty((b, cout // 8, 2 * h, 2 * w, 8), dtype=torch.float16, device=dev)
-        sl = torch.empty_like(sh) if nterms == 3 else None
+        split = SplitActivation.empty(b, cout, 2 * h, 2 * w, dev, want_lo=nterms == 3)
     else:
         out = torch.empty((b, cout, 2 * h, 2 * w), dtype=torch.float32, device=dev)
     kx, ky = factors
     nb_alg = float(b) * (4.0 * cin * h * w + 4.0 * cout * 4 * h * w + 4.0 * 4 * h * w) + 4.0 * 9 * cin * cout  # input, output, noise, weights
     code = _launch_profiled(
         lib, 2.0 * cin * cout * 9 * h * w * b,
-        lambda: lib.hf_modconv3x3_up_blur_f16_f32(_p(out), _p(sh), _p(sl), None if pre else _p(x), _p(x.hi) if pre else None,
+        lambda: lib.hf_modconv3x3_up_blur_f16_f32(_p(out), *_hl(split), None if pre else _p(x), _p(x.hi) if pre else None,
                                                   _p(x.lo) if (pre and nterms == 3) else None, _p(wt_hi),
                                                   _p(wt_lo) if nterms == 3 else None, None if pre else _p(s), _p(d),
                                                   kx, ky, _p(noise), _p(_c(noise_w)), nbs, _p(_c(bias)), _p(s_next), b, cin, cout,
                                                   h, w, alpha, scale, st), nbytes=nb_alg)
     check(lib, code, "hf_modconv3x3_up_blur_f16_f32")
-    return out if split_for is None else SplitActivation(sh, sl, None)
+    return out if split_for is None else split
 
 
 def torgb(lib, st, x, wt, s, bias, skip, up_kernel):
@@ -670,34 +683,64 @@ def bn_fold(lib, st, gamma, beta, mean, var, eps, conv_bias=None):
     return scale, shift
 
 
+def _enc_conv_io(lib, x, cout, stride, in_scale, in_shift, residual, groups=1, x_shared=True, ws_floats=None, taps=9, nterms=3,
+                 want_f32=True, split_out=False):
+    """What the four encoder conv wrappers share.  Parses x - fp32 [B,cin,H,W], grouped [G,B,cin,H,W] (groups > 1, not
+    x_shared), or a SplitActivation of B (grouped: G*B) images that carries its affine already -, allocates the fp32 output
+    (want_f32) and the workspace that ws_floats = (size query's name, arguments it takes between w and stride...) asks for,
+    checks the residual against the output shape and models the algorithmic HBM bytes (bench.py: traffic / algorithmic): the
+    pixels read (a shared input of a grouped launch once), every output form, a residual and the weights - each once.
+    Returns (x, (b, cin, h, w, oh, ow), x_gstride, out, residual, ws, floats in ws, nbytes)."""
+    pre = isinstance(x, SplitActivation)
+    own = groups > 1 and not x_shared  # every group reads its own input
+    if pre:
+        if in_scale is not None or in_shift is not None:
+            raise ValueError("a pre-split input carries its affine already")
+        n_img, cin, h, w = x.shape
+        b = n_img // groups if own else n_img
+        x_gstride = 1 if own else 0
+        dev = x.hi.device
+    else:
+        x = _c(x)
+        dev = x.device
+        if own:
+            g_, b, cin, h, w = x.shape
+            if g_ != groups:
+                raise ValueError("x must be [groups, B, cin, H, W]")
+            x_gstride = b * cin * h * w
+        else:
+            b, cin, h, w = x.shape
+            x_gstride = 0
+    oh, ow = (h - 1) // stride + 1, (w - 1) // stride + 1
+    shape = (groups, b, cout, oh, ow) if groups > 1 else (b, cout, oh, ow)
+    out = torch.empty(shape, dtype=torch.float32, device=dev) if want_f32 else None
+    if residual is not None:
+        residual = _c(residual)
+        if tuple(residual.shape) != shape:
+            raise ValueError(f"residual {tuple(residual.shape)} != output {shape}")
+    n = 0 if ws_floats is None else getattr(lib, ws_floats[0])(b, cin, cout, h, w, *ws_floats[1:], stride, groups)
+    ws = torch.empty((n,), dtype=torch.float32, device=dev) if n > 0 else None
+    nparts = 2 if nterms == 3 else 1
+    nb = (float(b * (groups if own else 1)) * cin * (h * w if taps == 9 else oh * ow) * (2.0 * nparts if pre else 4.0)
+          + float(b) * groups * cout * oh * ow * ((2.0 * nparts if split_out else 0.0) + (4.0 if want_f32 else 0.0)
+                                                  + (4.0 if residual is not None else 0.0))
+          + 2.0 * nparts * taps * cin * cout * groups)
+    return x, (b, cin, h, w, oh, ow), x_gstride, out, residual, ws, max(n, 0), nb
+
+
 def conv2d(lib, st, x, wt, k, stride=1, in_scale=None, in_shift=None, out_scale=None, bias=None, act=ACT_NONE,
            slope=None, alpha=0.0, residual=None, groups=1, x_shared=True):
     """groups == 1: x [B,cin,H,W], wt [k*k,cin,cout] -> [B,cout,oh,ow].
     groups  > 1: wt [G,k*k,cin,cout], bias/out_scale/slope [G,cout]; x [B,cin,H,W] shared by all
     groups (x_shared) or [G,B,cin,H,W]; returns [G,B,cout,oh,ow]."""
-    x = _c(x)
-    if groups > 1 and not x_shared:
-        g_, b, cin, h, w = x.shape
-        if g_ != groups:
-            raise ValueError("x must be [groups, B, cin, H, W]")
-        x_gstride = b * cin * h * w
-    else:
-        b, cin, h, w = x.shape
-        x_gstride = 0
     cout = wt.shape[-1]
-    oh, ow = (h - 1) // stride + 1, (w - 1) // stride + 1
-    out = x.new_empty((groups, b, cout, oh, ow) if groups > 1 else (b, cout, oh, ow))
-    if residual is not None:
-        residual = _c(residual)
-        if tuple(residual.shape) != tuple(out.shape):
-            raise ValueError(f"residual {tuple(residual.shape)} != output {tuple(out.shape)}")
-    n = lib.hf_conv2d_workspace_floats(b, cin, cout, h, w, k, stride, groups)
-    ws = x.new_empty((n,)) if n > 0 else None
+    x, (b, cin, h, w, oh, ow), x_gstride, out, residual, ws, n, _ = _enc_conv_io(
+        lib, x, cout, stride, None, None, residual, groups, x_shared, ("hf_conv2d_workspace_floats", k))
     code = _launch_profiled(
         lib, 2.0 * cin * cout * k * k * oh * ow * b * groups,
         lambda: lib.hf_conv2d_f32(_p(out), _p(x), _p(_c(wt)), _p(in_scale), _p(in_shift), _p(_c(out_scale)), _p(_c(bias)),
                                   act, _p(_c(slope)), float(alpha), _p(residual), b, cin, cout, h, w, k, stride, groups,
-                                  x_gstride, _p(ws), max(n, 0), st))
+                                  x_gstride, _p(ws), n, st))
     check(lib, code, "hf_conv2d_f32")
     return out
 
@@ -747,40 +790,14 @@ def conv1x1_f16(lib, st, x, wt_hi, wt_lo, nterms, cout, stride=1, in_scale=None,
     """hf_conv1x1_f16_f32: a 1x1 conv / Linear layer as a GEMM on the fp16 matrix cores; argument meaning as conv2d().
     x may be a SplitActivation (stride 1, no groups, affine already applied)."""
     pre = isinstance(x, SplitActivation)
-    if pre:
-        b, cin, h, w = x.shape
-        x_gstride = 0
-        proto = x.hi
-    else:
-        x = proto = _c(x)
-    if pre:
-        pass
-    elif groups > 1 and not x_shared:
-        g_, b, cin, h, w = x.shape
-        if g_ != groups:
-            raise ValueError("x must be [groups, B, cin, H, W]")
-        x_gstride = b * cin * h * w
-    else:
-        b, cin, h, w = x.shape
-        x_gstride = 0
-    oh, ow = (h - 1) // stride + 1, (w - 1) // stride + 1
-    out = torch.empty((groups, b, cout, oh, ow) if groups > 1 else (b, cout, oh, ow), dtype=torch.float32, device=proto.device)
-    if residual is not None:
-        residual = _c(residual)
-        if tuple(residual.shape) != tuple(out.shape):
-            raise ValueError(f"residual {tuple(residual.shape)} != output {tuple(out.shape)}")
-    n = lib.hf_conv1x1_f16_workspace_floats(b, cin, cout, h, w, stride, groups)
-    ws = torch.empty((n,), dtype=torch.float32, device=proto.device) if n > 0 else None
-    nparts = 2 if nterms == 3 else 1  # algorithmic HBM bytes: the pixels the GEMM reads, the output, a residual, the weights - each once
-    n_in = b * (1 if (groups == 1 or x_gstride == 0) else groups)
-    nb = (float(n_in) * cin * oh * ow * (2.0 * nparts if pre else 4.0) + float(b) * groups * cout * oh * ow * (4.0 + (4.0 if residual is not None else 0.0))
-          + 2.0 * nparts * cin * cout * groups)
+    x, (b, cin, h, w, oh, ow), x_gstride, out, residual, ws, n, nb = _enc_conv_io(
+        lib, x, cout, stride, in_scale, in_shift, residual, groups, x_shared, ("hf_conv1x1_f16_workspace_floats",), taps=1, nterms=nterms)
     code = _launch_profiled(
         lib, 2.0 * cin * cout * oh * ow * b * groups,
         lambda: lib.hf_conv1x1_f16_f32(_p(out), None if pre else _p(x), _p(x.hi) if pre else None, _p(x.lo) if pre else None,
                                        _p(wt_hi), _p(wt_lo), nterms, _p(_c(in_scale)), _p(_c(in_shift)),
                                        _p(_c(out_scale)), _p(_c(bias)), act, _p(_c(slope)), float(alpha), _p(residual), b, cin, cout,
-                                       h, w, stride, groups, x_gstride, _p(ws), max(n, 0), st),
+                                       h, w, stride, groups, x_gstride, _p(ws), n, st),
         label="gemm_h", nbytes=nb)
     check(lib, code, "hf_conv1x1_f16_f32")
     return out
@@ -792,11 +809,10 @@ def split_activation_f16(lib, st, x, in_scale=None, in_shift=None, want_lo=True)
     x = _c(x)
     c, h, w = x.shape[-3:]
     images = x.numel() // (c * h * w)
-    hi = torch.empty((images, c // 8, h, w, 8), dtype=torch.float16, device=x.device)
-    lo = torch.empty_like(hi) if want_lo else None
-    check(lib, lib.hf_split_activation_f16(_p(hi), _p(lo), _p(x), _p(_c(in_scale)), _p(_c(in_shift)), images, c, h, w, st),
+    split = SplitActivation.empty(images, c, h, w, x.device, want_lo)
+    check(lib, lib.hf_split_activation_f16(*_hl(split), _p(x), _p(_c(in_scale)), _p(_c(in_shift)), images, c, h, w, st),
           "hf_split_activation_f16")
-    return SplitActivation(hi, lo, None)
+    return split
 
 
 def conv2d_f16(lib, st, x, wt_hi, wt_lo, nterms, cout, stride=1, in_scale=None, in_shift=None, out_scale=None, bias=None,
@@ -805,44 +821,14 @@ def conv2d_f16(lib, st, x, wt_hi, wt_lo, nterms, cout, stride=1, in_scale=None, 
     x may be a SplitActivation (split_activation_f16 of the input, any in_scale / in_shift already applied):
     [B] images, or [groups*B] images with x_shared=False."""
     pre = isinstance(x, SplitActivation)
-    if pre:
-        if in_scale is not None or in_shift is not None:
-            raise ValueError("a pre-split input carries its affine already")
-        n_img, cin, h, w = x.shape
-        b = n_img if (groups == 1 or x_shared) else n_img // groups
-        x_gstride = 0 if (groups == 1 or x_shared) else 1
-        dev = x.hi.device
-    else:
-        x = _c(x)
-        dev = x.device
-        if groups > 1 and not x_shared:
-            g_, b, cin, h, w = x.shape
-            if g_ != groups:
-                raise ValueError("x must be [groups, B, cin, H, W]")
-            x_gstride = b * cin * h * w
-        else:
-            b, cin, h, w = x.shape
-            x_gstride = 0
-    oh, ow = (h - 1) // stride + 1, (w - 1) // stride + 1
-    out = torch.empty((groups, b, cout, oh, ow) if groups > 1 else (b, cout, oh, ow), dtype=torch.float32, device=dev)
-    if residual is not None:
-        residual = _c(residual)
-        if tuple(residual.shape) != tuple(out.shape):
-            raise ValueError(f"residual {tuple(residual.shape)} != output {tuple(out.shape)}")
-    n = lib.hf_conv2d_f16_workspace_floats(b, cin, cout, h, w, stride, groups)
-    ws = torch.empty((n,), dtype=torch.float32, device=dev) if n > 0 else None
-    # algorithmic HBM bytes (bench.py: traffic / algorithmic): the input once (a shared input of a grouped launch once), the
-    # output once, a residual once, the weights once
-    nparts = 2 if nterms == 3 else 1
-    n_in = b * (1 if (groups == 1 or x_gstride == 0) else groups)
-    nb = (float(n_in) * cin * h * w * (2.0 * nparts if pre else 4.0) + float(b) * groups * cout * oh * ow * (4.0 + (4.0 if residual is not None else 0.0))
-          + 2.0 * nparts * 9 * cin * cout * groups)
+    x, (b, cin, h, w, oh, ow), x_gstride, out, residual, ws, n, nb = _enc_conv_io(
+        lib, x, cout, stride, in_scale, in_shift, residual, groups, x_shared, ("hf_conv2d_f16_workspace_floats",), nterms=nterms)
     code = _launch_profiled(
         lib, 2.0 * cin * cout * 9 * oh * ow * b * groups,
         lambda: lib.hf_conv2d_f16_f32(_p(out), None if pre else _p(x), _p(x.hi) if pre else None, _p(x.lo) if pre else None,
                                       _p(wt_hi), _p(wt_lo), nterms, _p(in_scale), _p(in_shift), _p(_c(out_scale)),
                                       _p(_c(bias)), act, _p(_c(slope)), float(alpha), _p(residual), b, cin, cout, h, w, stride,
-                                      groups, x_gstride, _p(ws), max(n, 0), st), tag=",pre" if pre else "", nbytes=nb)
+                                      groups, x_gstride, _p(ws), n, st), tag=",pre" if pre else "", nbytes=nb)
     check(lib, code, "hf_conv2d_f16_f32")
     return out
 
@@ -858,36 +844,18 @@ def conv2d_f16_split(lib, st, x, wt_hi, wt_lo, nterms, cout, stride=1, in_scale=
     """hf_conv2d_f16_split_f32: conv2d_f16 whose result leaves as a SplitActivation (next_scale * y + next_shift, fp16 hi / lo,
     K-blocked) for the next fp16-core conv; want_f32: also the fp32 tensor -> (SplitActivation, out | None)."""
     pre = isinstance(x, SplitActivation)
-    if pre:
-        if in_scale is not None or in_shift is not None:
-            raise ValueError("a pre-split input carries its affine already")
-        b, cin, h, w = x.shape
-        dev = x.hi.device
-    else:
-        x = _c(x)
-        dev = x.device
-        b, cin, h, w = x.shape
-    oh, ow = (h - 1) // stride + 1, (w - 1) // stride + 1
-    out = torch.empty((b, cout, oh, ow), dtype=torch.float32, device=dev) if want_f32 else None
-    hi = torch.empty((b, cout // 8, oh, ow, 8), dtype=torch.float16, device=dev)
-    lo = torch.empty_like(hi) if nterms == 3 else None
-    if residual is not None:
-        residual = _c(residual)
-        if tuple(residual.shape) != (b, cout, oh, ow):
-            raise ValueError(f"residual {tuple(residual.shape)} != output {(b, cout, oh, ow)}")
-    nparts = 2 if nterms == 3 else 1  # algorithmic HBM bytes: input, split output (+ the fp32 one), residual, weights - each once
-    nb = (float(b) * cin * h * w * (2.0 * nparts if pre else 4.0)
-          + float(b) * cout * oh * ow * (2.0 * nparts + (4.0 if want_f32 else 0.0) + (4.0 if residual is not None else 0.0))
-          + 2.0 * nparts * 9 * cin * cout)
+    x, (b, cin, h, w, oh, ow), _, out, residual, _, _, nb = _enc_conv_io(
+        lib, x, cout, stride, in_scale, in_shift, residual, nterms=nterms, want_f32=want_f32, split_out=True)
+    split = SplitActivation.empty(b, cout, oh, ow, (x.hi if pre else x).device, want_lo=nterms == 3)
     code = _launch_profiled(
         lib, 2.0 * cin * cout * 9 * oh * ow * b,
-        lambda: lib.hf_conv2d_f16_split_f32(_p(out), _p(hi), _p(lo), _p(_c(next_scale)), _p(_c(next_shift)), None if pre else _p(x),
+        lambda: lib.hf_conv2d_f16_split_f32(_p(out), *_hl(split), _p(_c(next_scale)), _p(_c(next_shift)), None if pre else _p(x),
                                             _p(x.hi) if pre else None, _p(x.lo) if pre else None, _p(wt_hi), _p(wt_lo), nterms,
                                             _p(in_scale), _p(in_shift), _p(_c(out_scale)), _p(_c(bias)), act, _p(_c(slope)),
                                             float(alpha), _p(residual), b, cin, cout, h, w, stride, st),
         tag=",pre,split-out" if pre else ",split-out", nbytes=nb)
     check(lib, code, "hf_conv2d_f16_split_f32")
-    return SplitActivation(hi, lo, None), out
+    return split, out
 
 
 def plane_mean(lib, st, x):
@@ -923,11 +891,10 @@ def scale_shortcut_add_split(lib, st, r, gate, shortcut, sc_stride=1, next_scale
     b, c, oh, ow = r.shape
     sh, sw = shortcut.shape[2], shortcut.shape[3]
     out = torch.empty_like(r)
-    hi = torch.empty((b, c // 8, oh, ow, 8), dtype=torch.float16, device=r.device)
-    lo = torch.empty_like(hi) if want_lo else None
-    check(lib, lib.hf_scale_shortcut_add_split_f16(_p(out), _p(hi), _p(lo), _p(_c(next_scale)), _p(_c(next_shift)), _p(r), _p(gate),
+    split = SplitActivation.empty(b, c, oh, ow, r.device, want_lo)
+    check(lib, lib.hf_scale_shortcut_add_split_f16(_p(out), *_hl(split), _p(_c(next_scale)), _p(_c(next_shift)), _p(r), _p(gate),
                                                    _p(shortcut), sc_stride, b, c, oh, ow, sh, sw, st), "hf_scale_shortcut_add_split_f16")
-    return out, SplitActivation(hi, lo, None)
+    return out, split
 
 
 def upsample_bilinear_add(lib, st, x, y):

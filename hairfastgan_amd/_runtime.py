@@ -128,6 +128,11 @@ def conv_precision():
     return "f16x3" if _conv_precision == "auto" else _conv_precision
 
 
+def conv_nterms():
+    """fp16 MFMAs per product the fp16-core kernels run in the current mode: 3 = split (hi, lo) operands, 1 = plain fp16."""
+    return 3 if conv_precision() == "f16x3" else 1
+
+
 def configured_conv_precision():
     return _conv_precision
 

@@ -8,7 +8,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from .. import _marshal as M
-from .._runtime import conv_precision, lib, plan_batch, require_gpu, stream
+from .._runtime import conv_nterms, conv_precision, lib, require_gpu, stream
 
 
 class FrozenPlanMixin:
@@ -116,16 +116,19 @@ USE_GEMM_H = os.environ.get("HAIRFAST_GEMM_H", "1") != "0"
 USE_PAIR = os.environ.get("HAIRFAST_CONV_PAIR", "1") != "0"
 
 
-def _small_plane_conv(x, w, mode, kw):
+def _small_plane_takes(kw):
+    """The tap GEMM's combine pass has one epilogue: bias (+ leaky ReLU)."""
+    act = kw.get("act", M.ACT_NONE)
+    return not (set(kw) - {"bias", "act", "alpha"}) and (act == M.ACT_NONE or (act == M.ACT_LRELU and kw.get("bias") is not None))
+
+
+def _small_plane_conv(x, w, kw):
     """A dense 3x3 stride-1 conv on planes too small for the tiled fp16-core kernel (under 16 columns: the CtrlHair shape
     adaptor's 4^2 / 8^2 layers with 1024-2048 channels, 75-150 MB of weights each) as the tap GEMM of csrc/gemm_h.hip -
     weight streaming with (tap, channel tile, K split) spread over the chip; the fp32-MFMA kernel took 420-680 us per layer
-    at batch 16.  None when the call has an epilogue the combine pass does not have."""
-    act = kw.get("act", M.ACT_NONE)
-    if (set(kw) - {"bias", "act", "alpha"}) or act not in (M.ACT_NONE, M.ACT_LRELU) or (act == M.ACT_LRELU and kw.get("bias") is None):
-        return None
-    alpha = float(kw.get("alpha", 0.0)) if act == M.ACT_LRELU else 1.0
-    return M.modconv3x3_small(lib(), stream(), x, w.small(), 3 if mode == "f16x3" else 1, None, None, None, None, kw.get("bias"),
+    at batch 16.  For calls whose epilogue the combine pass has (_small_plane_takes)."""
+    alpha = float(kw.get("alpha", 0.0)) if kw.get("act", M.ACT_NONE) == M.ACT_LRELU else 1.0
+    return M.modconv3x3_small(lib(), stream(), x, w.small(), conv_nterms(), None, None, None, None, kw.get("bias"),
                               w.cout, alpha=alpha, scale=1.0)
 
 
@@ -142,7 +145,7 @@ def patches(x, k, stride, pad, tap_major=True):
     return torch.stack(taps, dim=-3).reshape(*x.shape[:-3], x.shape[-3] * k * k, oh, ow)
 
 
-def _patch_gemm_conv(x, w, mode, stride, kw):
+def _patch_gemm_conv(x, w, stride, kw):
     """A 3x3 conv whose OUTPUT planes are at most 8x8 (the e4e style heads' stride-2 chains 16^2 -> 8^2 -> ... -> 1, eleven
     heads per grouped launch, 9.4 MB of weights per head and level) as a GEMM over unfolded patches on the fp16 matrix
     cores: K = cin*9 with exactly the needed flops, (group, channel tile, image pair) blocks over the chip.  The patches
@@ -153,20 +156,48 @@ def _patch_gemm_conv(x, w, mode, stride, kw):
     cols = patches(x, 3, stride, 1).reshape(*x.shape[:-3], 9 * cin, 1, oh * ow)              # K = (tap, ci)
     hi, lo = w.patch()
     rest = {k_: v for k_, v in kw.items() if k_ not in ("groups", "x_shared")}
-    y = M.conv1x1_f16(lib(), stream(), cols, hi, lo, 3 if mode == "f16x3" else 1, w.cout, 1, groups=groups, x_shared=shared, **rest)
+    y = M.conv1x1_f16(lib(), stream(), cols, hi, lo, conv_nterms(), w.cout, 1, groups=groups, x_shared=shared, **rest)
     return y.reshape(*y.shape[:-2], oh, ow)
+
+
+# The kernel families conv() chooses between.  They sum in different orders: the route decides a sample's bits.
+PRE_SPLIT, GEMM_1X1, PATCH_GEMM, SMALL_PLANE, TILED_F16, FP32 = "pre-split", "gemm-1x1", "patch-gemm", "small-plane", "tiled-f16", "fp32"
+
+
+def conv_route(w, h, wd, k, stride, kw, x_is_split=False, batch=None):
+    """The ONE place that decides which kernel runs a conv() call with epilogue / grouping arguments kw on h x wd planes:
+      PRE_SPLIT    a SplitActivation handed over by the producer: only the tiled fp16-core kernel reads it
+      GEMM_1X1     1x1 conv / Linear as a GEMM on the fp16 matrix cores (hf_conv1x1_f16_f32)
+      PATCH_GEMM   stride-2 3x3 conv with output planes under 8x8 as a GEMM over unfolded patches (_patch_gemm_conv)
+      SMALL_PLANE  dense 3x3 conv on planes the tiled kernel does not take, as the tap GEMM (_small_plane_conv); needs
+                   batch = the images of a plain [B,cin,H,W] input (None: grouped input, or the caller only asks whether
+                   the call is TILED_F16, which excludes this route)
+      TILED_F16    the tiled fp16-core 3x3 kernel (hf_conv2d_f16_f32): accepts a pre-split input, can emit a split output
+      FP32         the fp32-MFMA general kernel: mode f32 and every shape nothing above takes."""
+    mode = conv_precision()
+    if x_is_split:
+        if k != 3 or mode == "f32":
+            raise ValueError("a pre-split input goes to a 3x3 conv on the fp16 matrix cores (takes_f16_conv)")
+        return PRE_SPLIT
+    if mode == "f32":
+        return FP32
+    if k == 1 and USE_GEMM_H and M.conv1x1_f16_supported(w.cin, w.cout):
+        return GEMM_1X1
+    if (k == 3 and USE_GEMM_H and h <= 16 and wd <= 16 and (h - 1) // stride < 8 and (wd - 1) // stride < 8
+            and w.cin % 32 == 0 and w.cout % 64 == 0 and w.cin * w.cout >= 256 * 256 and stride == 2
+            and not ({"in_scale", "in_shift", "residual"} & set(kw))):
+        return PATCH_GEMM
+    tiled = M.conv2d_f16_supported(w.cin, w.cout, h, wd, k, stride)
+    if (k == 3 and stride == 1 and batch is not None and not tiled and M.conv3x3_small_supported(w.cin, w.cout, h, wd, batch)
+            and _small_plane_takes(kw)):
+        return SMALL_PLANE
+    return TILED_F16 if tiled else FP32
 
 
 def takes_f16_conv(w, h, wd, k, stride, **kw):
     """Does conv() run this call on the tiled fp16-core 3x3 kernel (hf_conv2d_f16_f32) - the one that accepts a pre-split input
-    and can emit a split output?  (The same tests as conv()'s dispatch, in its order.)"""
-    mode = conv_precision()
-    if mode == "f32" or k != 3:
-        return False
-    if (USE_GEMM_H and h <= 16 and wd <= 16 and (h - 1) // stride < 8 and (wd - 1) // stride < 8 and w.cin % 32 == 0
-            and w.cout % 64 == 0 and w.cin * w.cout >= 256 * 256 and stride == 2 and not ({"in_scale", "in_shift", "residual"} & set(kw))):
-        return False  # patch GEMM
-    return M.conv2d_f16_supported(w.cin, w.cout, h, wd, k, stride)
+    and can emit a split output?"""
+    return conv_route(w, h, wd, k, stride, kw) == TILED_F16
 
 
 def conv(x, w, k, stride=1, presplit=False, split_out=None, **kw):
@@ -192,63 +223,57 @@ def conv(x, w, k, stride=1, presplit=False, split_out=None, **kw):
     return _conv_unpadded(x, w, k, stride, presplit, split_out, **kw)
 
 
+def _many_block_columns(x, w, h, wd, stride, groups=1):
+    """PRESPLIT "all": is a 3x3 conv's input worth a separate split pass - the same input tile would be converted by many
+    (group, 64-channel) block columns, or, from 128 input channels, a batched pass (HairFast.swap_batch) makes the extra
+    launch negligible (tools/bench_enc_layers.py, ENC_BATCH_MULT=8: 256->256 @32^2 128 -> 111 us, 512->512 stride 2 340 -> 160 us).
+    Bit-neutral, so the real batch decides in every mode."""
+    out_px = x.shape[0] * ((h - 1) // stride + 1) * ((wd - 1) // stride + 1)
+    return PRESPLIT == "all" and (groups * (w.cout // 64) >= 8 or (w.cin >= 128 and out_px >= 12288))
+
+
+def _split_input(x, kw, nterms):
+    """Convert a conv's input once (hf_split_activation_f16): the kernel then stages it by LDS-DMA instead of converting it in
+    every block column.  The input affine goes into the split and leaves kw."""
+    return M.split_activation_f16(lib(), stream(), x, kw.pop("in_scale", None), kw.pop("in_shift", None), want_lo=nterms == 3)
+
+
 def _conv_unpadded(x, w, k, stride=1, presplit=False, split_out=None, **kw):
-    mode = conv_precision()
     h, wd = x.shape[-2], x.shape[-1]
+    pre = isinstance(x, M.SplitActivation)
+    nterms = conv_nterms()
+    groups = kw.get("groups", 1)
     if split_out is not None:
         b = x.shape[0]
-        nterms = 3 if mode == "f16x3" else 1
-        out_px = b * ((h - 1) // stride + 1) * ((wd - 1) // stride + 1)  # (bit-neutral: the real batch in every mode)
-        to_split = (not isinstance(x, M.SplitActivation) and PRESPLIT == "all"
-                    and (w.cout // 64 >= 8 or (w.cin >= 128 and out_px >= 12288)))
-        if (kw.get("groups", 1) == 1 and takes_f16_conv(w, h, wd, k, stride, **kw)
-                and M.conv2d_f16_split_supported(lib(), b, w.cin, w.cout, h, wd, stride, nterms,
-                                                 pre=to_split or isinstance(x, M.SplitActivation))):
+        to_split = not pre and _many_block_columns(x, w, h, wd, stride)
+        if (groups == 1 and takes_f16_conv(w, h, wd, k, stride, **kw)
+                and M.conv2d_f16_split_supported(lib(), b, w.cin, w.cout, h, wd, stride, nterms, pre=to_split or pre)):
             hi, lo = w.f16()
             if to_split:
-                x = M.split_activation_f16(lib(), stream(), x, kw.pop("in_scale", None), kw.pop("in_shift", None), want_lo=nterms == 3)
+                x = _split_input(x, kw, nterms)
             return M.conv2d_f16_split(lib(), stream(), x, hi, lo, nterms, w.cout, stride, next_scale=split_out.get("next_scale"),
                                       next_shift=split_out.get("next_shift"), want_f32=split_out.get("want_f32", False), **kw)
         return None, _conv_unpadded(x, w, k, stride, presplit, **kw)
-    if isinstance(x, M.SplitActivation):  # a hand-off from the producing conv: only the tiled fp16-core kernel reads it
-        if k != 3 or mode == "f32":
-            raise ValueError("a pre-split input goes to a 3x3 conv on the fp16 matrix cores (takes_f16_conv)")
+    route = conv_route(w, h, wd, k, stride, kw, pre, None if pre or x.dim() != 4 else x.shape[0])
+    if route in (PRE_SPLIT, TILED_F16):
         hi, lo = w.f16()
-        return M.conv2d_f16(lib(), stream(), x, hi, lo, 3 if mode == "f16x3" else 1, w.cout, stride, **kw)
-    if mode != "f32" and k == 1 and USE_GEMM_H and M.conv1x1_f16_supported(w.cin, w.cout):
+        if not pre and (_many_block_columns(x, w, h, wd, stride, groups) or (presplit and PRESPLIT in ("all", "heads"))):
+            x = _split_input(x, kw, nterms)
+        return M.conv2d_f16(lib(), stream(), x, hi, lo, nterms, w.cout, stride, **kw)
+    if route == GEMM_1X1:
         hi, lo = w.f16()
-        nterms = 3 if mode == "f16x3" else 1
-        # one input feeding >= 8 output-channel tiles over enough pixels: convert it once (hf_split_activation_f16), the
-        # GEMM then stages it by LDS-DMA instead of converting it in every block column
+        # a different rule from the 3x3 one: one input feeding >= 8 output-channel tiles over enough pixels
         # (from 32 tiles already at 128 pixels: SEAN's table GEMM - 288 channel tiles over 304 label columns - spent 3/4 of its
         # 160 us converting the same 512 x 304 input in every block column)
         px = x.shape[0] * h * wd  # pre-split or register-staged input: equal results, so the whole launch decides in every mode
-        if (PRESPLIT == "all" and stride == 1 and kw.get("groups", 1) == 1 and w.cin % 8 == 0
+        if (PRESPLIT == "all" and stride == 1 and groups == 1 and w.cin % 8 == 0
                 and ((w.cout // 64 >= 8 and px >= 512) or (w.cout // 64 >= 32 and px >= 128))):
-            x = M.split_activation_f16(lib(), stream(), x, kw.pop("in_scale", None), kw.pop("in_shift", None), want_lo=nterms == 3)
+            x = _split_input(x, kw, nterms)
         return M.conv1x1_f16(lib(), stream(), x, hi, lo, nterms, w.cout, stride, **kw)
-    if (mode != "f32" and k == 3 and USE_GEMM_H and h <= 16 and wd <= 16 and (h - 1) // stride < 8 and (wd - 1) // stride < 8
-            and w.cin % 32 == 0 and w.cout % 64 == 0 and w.cin * w.cout >= 256 * 256 and stride == 2
-            and not ({"in_scale", "in_shift", "residual"} & set(kw))):
-        return _patch_gemm_conv(x, w, mode, stride, kw)
-    if (mode != "f32" and k == 3 and stride == 1 and x.dim() == 4 and not M.conv2d_f16_supported(w.cin, w.cout, h, wd, k, stride)
-            and M.conv3x3_small_supported(w.cin, w.cout, h, wd, x.shape[0])):
-        y = _small_plane_conv(x, w, mode, kw)
-        if y is not None:
-            return y
-    if mode != "f32" and M.conv2d_f16_supported(w.cin, w.cout, h, wd, k, stride):
-        hi, lo = w.f16()
-        nterms = 3 if mode == "f16x3" else 1
-        groups = kw.get("groups", 1)
-        # worth a separate pass when the same input tile is converted by many (group, 64-channel) block columns -
-        # or, from 128 input channels, when a batched pass (HairFast.swap_batch) makes the extra launch negligible
-        # (tools/bench_enc_layers.py, ENC_BATCH_MULT=8: 256->256 @32^2 128 -> 111 us, 512->512 stride 2 340 -> 160 us)
-        out_px = x.shape[0] * ((h - 1) // stride + 1) * ((wd - 1) // stride + 1)  # (bit-neutral: the real batch)
-        many = groups * (w.cout // 64) >= 8 or (w.cin >= 128 and out_px >= 12288)
-        if not isinstance(x, M.SplitActivation) and ((PRESPLIT == "all" and many) or (presplit and PRESPLIT in ("all", "heads"))):
-            x = M.split_activation_f16(lib(), stream(), x, kw.pop("in_scale", None), kw.pop("in_shift", None),
-                                       want_lo=nterms == 3)
-        return M.conv2d_f16(lib(), stream(), x, hi, lo, nterms, w.cout, stride, **kw)
+    if route == PATCH_GEMM:
+        return _patch_gemm_conv(x, w, stride, kw)
+    if route == SMALL_PLANE:
+        return _small_plane_conv(x, w, kw)
     return M.conv2d(lib(), stream(), x, w.wt, k, stride, **kw)
 
 
@@ -279,7 +304,7 @@ def conv_pair(x, w1, kw1, w2, stride2, kw2, stride1=1, out_split=None):
     return conv(mid, w2, 3, stride2, split_out=dict(out_split, want_f32=True), **kw2)
 
 
-def chain_takes_split(w1, h, wd, **kw1):
+def chain_takes_split(w1, h, wd, stride=1, **kw1):
     """Will the first 3x3 conv of a unit accept a pre-split input handed over by its predecessor (the tiled fp16-core kernel
-    runs it)?"""
-    return USE_CHAIN and takes_f16_conv(w1, h, wd, 3, 1, **kw1)
+    runs it; stride 2: its pre-split stride-2 form)?"""
+    return USE_CHAIN and takes_f16_conv(w1, h, wd, 3, stride, **kw1)

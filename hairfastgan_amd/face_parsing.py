@@ -22,10 +22,7 @@ from torch import nn
 
 from . import _marshal as M
 from ._runtime import conv_precision, lib, require_gpu, stream
-from .encoders._fused import FrozenPlanMixin, chain_takes_split, conv, conv_pair, fold_bn, prep_conv, takes_f16_conv
-from .encoders import _fused
-
-USE_CHAIN_STRIDED = True  # hand-over into a stride-2 first conv (pre-split stride-2 form)
+from .encoders._fused import FrozenPlanMixin, chain_takes_split, conv, conv_pair, fold_bn, prep_conv
 
 # FaceParsing_tensor.label_list order -> index in PARSING_LABEL_LIST (global_value_utils.py:49-51); 13 = hair
 _BISENET_LABELS = ["background", "skin_other", "l_brow", "r_brow", "l_eye", "r_eye", "eye_g", "l_ear", "r_ear", "ear_r",
@@ -93,8 +90,7 @@ class BasicBlock(nn.Module):  # resnet.py:19-46
 
     def takes_split(self, p, h, wd):
         """Would this block's first conv accept its input pre-split (handed over by the previous block's second conv)?"""
-        return chain_takes_split(p["w1"], h, wd, out_scale=p["bn1"][0], bias=p["bn1"][1], **RELU) if self.stride == 1 else \
-            (USE_CHAIN_STRIDED and _fused.USE_CHAIN and takes_f16_conv(p["w1"], h, wd, 3, self.stride, out_scale=p["bn1"][0], bias=p["bn1"][1], **RELU))
+        return chain_takes_split(p["w1"], h, wd, self.stride, out_scale=p["bn1"][0], bias=p["bn1"][1], **RELU)
 
     def run_chain(self, p, x, xs, hand_over):
         """xs: x in conv1's pre-split layout (the previous block's hand-over) or None; hand_over: also return the result

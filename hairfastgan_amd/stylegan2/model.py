@@ -25,7 +25,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from .. import _marshal as M
-from .._runtime import conv_precision, lib, reference_rng_walk, require_gpu, run_guarded, stream
+from .._runtime import conv_nterms, conv_precision, lib, reference_rng_walk, require_gpu, run_guarded, stream
 from .op import FusedLeakyReLU, fused_leaky_relu, upfirdn2d
 
 
@@ -177,30 +177,58 @@ class ModulatedConv2d(nn.Module):  # :183-279
             cached = self.__dict__["_prep_small"] = (key, M.split_weights_small(lib(), stream(), wt))
         return cached[1]
 
+    # -- kernel routes: every decision that picks a kernel family (and with it a sample's bits) is made here, once ---------
+    def route_same_res(self, shape, plain=True):
+        """Which kernel runs the same-resolution 3x3 conv on an input of `shape` [B,cin,H,W] in the process-wide mode
+        (_runtime.conv_precision), and whether the layer's ToRGB can be computed in its epilogue: (kernel, fuses_torgb).
+          "small"  small planes (the 4^2 - 32^2 tower at small batch): nine taps as one GEMM over the whole chip + a combine
+                   pass; plain=False rules it out - the call brings a pre-split input or wants a fused ToRGB
+          "f16"    the tiled fp16-core kernel, where it takes the shape and pays (batch-dependent); fuses_torgb: a wave sums
+                   the 64 / 32 output channels it holds, ToRGB.finish adds the slabs
+          "f32"    the fp32-MFMA kernel: mode f32 and every other shape."""
+        b, cin, h, w = shape
+        cout = self.out_channel
+        if conv_precision() == "f32":
+            return "f32", False
+        if plain and M.modconv3x3_small_supported(cin, cout, h, w, b):
+            return "small", False
+        if M.modconv3x3_f16_supported(cin, cout, h, w, batch=b):
+            return "f16", not self.upsample and self.kernel_size == 3 and M.torgb_fusable(cin, cout, h, w)
+        return "f32", False
+
+    def route_up(self, shape, is_split=False, tail=True):
+        """Which kernels run the upsampling conv on an input of `shape` (is_split: a SplitActivation):
+          "fused"  transposed conv + blur + noise + bias + lrelu in ONE kernel (hf_modconv3x3_up_blur_f16_f32: no (2h+1)^2
+                   intermediate) from FUSE_BLUR_MIN_H input rows, when the call has that tail and the blur is separable
+          "small"  small planes: the nine taps as one GEMM, then the blur pass
+          "f16"    two passes, the transposed conv on the fp16 matrix cores
+          "f32"    two passes, the transposed conv on the fp32 MFMA."""
+        b, cin, h, w = shape
+        cout = self.out_channel
+        if conv_precision() == "f32":
+            return "f32"
+        if h >= FUSE_BLUR_MIN_H and tail and M.modconv3x3_up_fused_supported(cin, cout, h, w) and self.blur_factors() is not None:
+            return "fused"
+        if not is_split and M.modconv3x3_small_supported(cin, cout, h, w, b, upsample=True):
+            return "small"
+        return "f16" if M.modconv3x3_up_f16_supported(cin, cout, h, w, batch=b) else "f32"
+
     def conv_same_res(self, input, wt, s, d, noise, noise_w, bias, alpha=0.2, scale=math.sqrt(2), rgb=None):
-        """3x3 same-resolution modulated conv (+ fused noise/bias/lrelu epilogue) on the matrix
-        cores the process-wide mode selects (_runtime.conv_precision).  rgb: see fuses_torgb."""
-        mode = conv_precision()
-        b_, cin, h, w = input.shape
-        if mode != "f32" and rgb is None and M.modconv3x3_small_supported(cin, self.out_channel, h, w, b_):
-            # small planes (the 4^2 - 32^2 tower at small batch): nine taps as one GEMM over the whole chip + a combine pass
-            return M.modconv3x3_small(lib(), stream(), input, self.prepared_small(), 3 if mode == "f16x3" else 1, s, d, noise,
-                                      noise_w, bias, self.out_channel, alpha, scale)
-        if mode != "f32" and M.modconv3x3_f16_supported(cin, self.out_channel, h, w, batch=b_):
+        """3x3 same-resolution modulated conv (+ fused noise/bias/lrelu epilogue) on the kernel route_same_res picks.
+        rgb: see fuses_torgb."""
+        kernel, _ = self.route_same_res(input.shape, plain=rgb is None)
+        if kernel == "small":
+            return M.modconv3x3_small(lib(), stream(), input, self.prepared_small(), conv_nterms(), s, d, noise, noise_w, bias,
+                                      self.out_channel, alpha, scale)
+        if kernel == "f16":
             hi, lo = self.prepared_f16()
-            return M.modconv3x3_f16(lib(), stream(), input, hi, lo, 3 if mode == "f16x3" else 1, s, d, noise,
-                                    noise_w, bias, alpha, scale, rgb=rgb)
+            return M.modconv3x3_f16(lib(), stream(), input, hi, lo, conv_nterms(), s, d, noise, noise_w, bias, alpha, scale, rgb=rgb)
         assert rgb is None
         return M.modconv3x3(lib(), stream(), input, wt, s, d, noise, noise_w, bias, alpha, scale)
 
     def fuses_torgb(self, input):
-        """True when the layer's ToRGB can be computed in this conv's epilogue (fp16-core modes; a wave sums the
-        64 / 32 output channels it holds, ToRGB.finish adds the slabs)."""
-        b_, cin, h, w = input.shape
-        # the same predicates conv_same_res dispatches on: the fp16-core kernel must be the one that runs (batch-dependent)
-        return (conv_precision() != "f32" and not self.upsample and self.kernel_size == 3
-                and M.torgb_fusable(cin, self.out_channel, h, w)
-                and M.modconv3x3_f16_supported(cin, self.out_channel, h, w, batch=b_))
+        """True when the layer's ToRGB can be computed in this conv's epilogue (route_same_res)."""
+        return self.route_same_res(input.shape, plain=False)[1]
 
     def blur_factors(self):
         """1-D factors of the module's blur kernel when it is separable (it is: make_kernel of a 1-D list,
@@ -215,27 +243,19 @@ class ModulatedConv2d(nn.Module):  # :183-279
         return cached[1]
 
     def conv_up(self, input, wt, s, d, noise, noise_w, bias, alpha=0.2, scale=math.sqrt(2), split_for=None):
-        """Transposed 3x3 conv + blur (+ fused noise/bias/lrelu), matrix cores per the mode.
-        split_for=(key, s_next): the blur pass writes a SplitActivation for the next conv.
-        Large planes in the fp16-core modes run the ONE-kernel form (hf_modconv3x3_up_blur_f16_f32: no (2h+1)^2
-        intermediate); FUSE_BLUR_MIN_H is the smallest input height that takes it."""
-        mode = conv_precision()
-        _, cin, h, w = input.shape
-        if (mode in ("f16x3", "f16") and h >= FUSE_BLUR_MIN_H and noise is not None and bias is not None and 0.0 <= alpha <= 1.0
-                and M.modconv3x3_up_fused_supported(cin, self.out_channel, h, w)):
-            fac = self.blur_factors()
-            if fac is not None:
-                hi, lo = self.prepared_f16()
-                return M.modconv3x3_up_fused(lib(), stream(), input, hi, lo, s, d, fac, noise, noise_w, bias, alpha, scale,
-                                             split_for=None if split_for is None else split_for[1],
-                                             nterms=3 if mode == "f16x3" else 1)
-        f16 = small = None
-        if (mode != "f32" and not isinstance(input, M.SplitActivation)
-                and M.modconv3x3_small_supported(cin, self.out_channel, h, w, input.shape[0], upsample=True)):
-            small = (self.prepared_small(), 3 if mode == "f16x3" else 1)  # small planes: the nine taps as one GEMM
-        elif mode != "f32" and M.modconv3x3_up_f16_supported(cin, self.out_channel, h, w, batch=input.shape[0]):
+        """Transposed 3x3 conv + blur (+ fused noise/bias/lrelu) on the kernels route_up picks.
+        split_for=(key, s_next): the blur pass writes a SplitActivation for the next conv."""
+        route = self.route_up(input.shape, isinstance(input, M.SplitActivation),
+                              tail=noise is not None and bias is not None and 0.0 <= alpha <= 1.0)
+        if route == "fused":
             hi, lo = self.prepared_f16()
-            f16 = (hi, lo, 3 if mode == "f16x3" else 1)
+            return M.modconv3x3_up_fused(lib(), stream(), input, hi, lo, s, d, self.blur_factors(), noise, noise_w, bias, alpha, scale,
+                                         split_for=None if split_for is None else split_for[1], nterms=conv_nterms())
+        f16 = small = None
+        if route == "small":
+            small = (self.prepared_small(), conv_nterms())
+        elif route == "f16":
+            f16 = (*self.prepared_f16(), conv_nterms())
         return M.modconv3x3_up(lib(), stream(), input, wt, s, d, self.blur.kernel, noise, noise_w, bias, alpha, scale,
                                f16=f16, split_for=split_for, small=small)
 
@@ -357,8 +377,7 @@ class StyledConv(nn.Module):  # :309-343
             noise = split.hi.new_empty(b, 1, h, w, dtype=torch.float32).normal_()
         require_gpu(noise, skip)
         hi, lo = conv.prepared_f16()
-        nterms = 3 if conv_precision() == "f16x3" else 1
-        return M.modconv3x3_f16_pre_image(lib(), stream(), split, hi, lo, nterms, d, noise, self.noise.weight.detach(),
+        return M.modconv3x3_f16_pre_image(lib(), stream(), split, hi, lo, conv_nterms(), d, noise, self.noise.weight.detach(),
                                           act.bias.detach(), rgb, to_rgb.bias.detach(), skip, to_rgb._skip_kernel(skip),
                                           act.negative_slope, act.scale)
 
@@ -378,15 +397,9 @@ class StyledConv(nn.Module):  # :309-343
         require_gpu(noise)
         act = self.activate
         hi, lo = conv.prepared_f16()
-        nterms = 3 if conv_precision() == "f16x3" else 1
-        res = M.modconv3x3_f16_pre(lib(), stream(), split, hi, lo, nterms, d, noise, self.noise.weight.detach(),
-                                   act.bias.detach(), act.negative_slope, act.scale, rgb=rgb, want_out=want_out,
-                                   split_for=split_for)
-        res = list(res) if isinstance(res, tuple) else [res]
-        out = res.pop(0)
-        raw = res.pop(0) if rgb is not None else None
-        nxt = res.pop(0) if split_for is not None else None
-        return out, raw, nxt
+        return M._modconv3x3_f16_pre(lib(), stream(), split, hi, lo, conv_nterms(), d, noise, self.noise.weight.detach(),
+                                     act.bias.detach(), act.negative_slope, act.scale, rgb=rgb, want_out=want_out,
+                                     split_for=split_for)
 
 
 def _observed(*modules):
@@ -577,6 +590,44 @@ class Generator(nn.Module):  # :368-565
             conv._coeffs = ((view.data_ptr(), tuple(view.shape), tuple(view.stride())), (conv.prepared()[0], sv, dv))
         return convs
 
+    def _fast_block(self, block, src, mid_shape, fuses, latent, noise, skip, up_coeffs, end_layer):
+        """One resolution block with the activations travelling between the convs pre-modulated, split into fp16 pairs and
+        K-blocked (M.SplitActivation): conv_up's blur pass writes conv_same's input, conv_same's epilogue writes the next
+        block's conv_up input; an fp32 activation is only materialised where something else reads it.  src: the block's
+        input (a SplitActivation from the block below, with up_coeffs the coefficients that went into it); mid_shape /
+        fuses: conv_same's input shape and route_same_res's verdict on its ToRGB.
+        Returns (out | None, skip, split for the next block | None, the next block's conv_up coefficients)."""
+        conv_up, conv_same, to_rgb = self.convs[2 * block - 2], self.convs[2 * block - 1], self.to_rgbs[block - 1]
+        i = 2 * block - 1
+        coeffs = conv_same.conv.style_coefficients(latent[:, i + 1])
+        split = conv_up.forward_split(src, latent[:, i], noise[2 * block - 1], coeffs[1],
+                                      coeffs=up_coeffs if isinstance(src, M.SplitActivation) else None)
+        rgb = to_rgb.coefficients(latent[:, i + 2]) if fuses else None
+        is_last = block == self.log_size - 2
+        s_up = None
+        if not is_last and block + 1 <= end_layer:  # will the next block run fast too and take its input pre-split?
+            nup, nsame = self.convs[2 * block], self.convs[2 * block + 1]
+            up_shape = (mid_shape[0], conv_same.conv.out_channel) + mid_shape[2:]
+            next_mid = (mid_shape[0], nup.conv.out_channel, 2 * mid_shape[2], 2 * mid_shape[3])
+            if (nup.conv.route_up(up_shape, is_split=True) != "f32" and nsame.conv.route_same_res(next_mid, plain=False)[0] == "f16"
+                    and not _observed(nup, nsame)):
+                up_coeffs = nup.conv.style_coefficients(latent[:, i + 2])
+                s_up = up_coeffs[1]
+        fused_rgb = rgb is not None and not _observed(to_rgb)
+        # fp32 activation: read by a stand-alone ToRGB, returned on an early exit, or fed to the next block as a plain tensor
+        want_out = not fused_rgb or (not is_last and s_up is None)
+        if (fused_rgb and not want_out and s_up is None and skip is not None and M.image_fusable(mid_shape[1], conv_same.conv.out_channel, *mid_shape[2:])
+                and conv_same.activate.bias is not None):
+            # the last layer: its epilogue finishes ToRGB (bias + upsampled skip) - no raw product, no finishing launch
+            image = conv_same.forward_image(split, coeffs, noise[2 * block], rgb, to_rgb, skip)
+            if image is not None:
+                return None, image, None, up_coeffs
+        out, raw, split_in = conv_same.forward_from_split(split, coeffs, noise[2 * block], rgb=rgb if fused_rgb else None,
+                                                          want_out=want_out, split_for=s_up)
+        # the raw 1x1 product travels as an explicit value from the producing conv to its ToRGB
+        skip = to_rgb.finish(raw, skip) if raw is not None else to_rgb(out, latent[:, i + 2], skip)
+        return out, skip, split_in, up_coeffs
+
     def _run_layers(self, latent, noise, layer_in, skip, start_layer, end_layer, return_latents):
         out = self.input(latent)
         if start_layer == 0:
@@ -584,69 +635,29 @@ class Generator(nn.Module):  # :368-565
             skip = self.to_rgb1(out, latent[:, 1])
         if end_layer == 0:
             return out, skip
-        i = 1
-        split_in = up_coeffs = None  # SplitActivation of `out` for the next block's transposed conv (fast path)
+        split_in = up_coeffs = None  # SplitActivation of `out` for the next block's transposed conv, and that conv's coefficients
         for block in range(1, self.log_size - 1):
-            conv_up, conv_same, to_rgb = self.convs[2 * block - 2], self.convs[2 * block - 1], self.to_rgbs[block - 1]
             if block < start_layer:
-                pass
-            elif block != start_layer and block > end_layer:
+                continue
+            if block != start_layer and block > end_layer:
                 return out, skip
+            conv_up, conv_same, to_rgb = self.convs[2 * block - 2], self.convs[2 * block - 1], self.to_rgbs[block - 1]
+            i = 2 * block - 1  # rows of W+: i, i + 1 the two convs, i + 2 the ToRGB (:529-545)
+            src = layer_in if block == start_layer else (split_in if split_in is not None else out)  # (`out` may not exist: want_out)
+            mid_shape = (src.shape[0], conv_up.conv.out_channel, 2 * src.shape[2], 2 * src.shape[3])
+            kernel, fuses = conv_same.conv.route_same_res(mid_shape, plain=False)
+            if kernel == "f16" and not _observed(conv_up, conv_same):
+                out, skip, split_in, up_coeffs = self._fast_block(block, src, mid_shape, fuses, latent, noise, skip, up_coeffs, end_layer)
             else:
-                src = layer_in if block == start_layer else out
-                if split_in is not None and block != start_layer:
-                    src = split_in  # the fp32 `out` may not even exist (see want_out below)
-                rgb_style = latent[:, i + 2]
-                cmid, csame = conv_up.conv.out_channel, conv_same.conv.out_channel
-                h2, w2 = 2 * src.shape[2], 2 * src.shape[3]
-                fast_mode = conv_precision() != "f32"
-                nb_ = src.shape[0]
-                if (fast_mode and cmid % 16 == 0 and M.modconv3x3_f16_supported(cmid, csame, h2, w2, batch=nb_)
-                        and not _observed(conv_up, conv_same)):
-                    # fast path: activations travel between the convs pre-modulated, split into fp16
-                    # pairs and K-blocked (M.SplitActivation) - conv_up's blur pass writes conv_same's
-                    # input, conv_same's epilogue writes the next block's conv_up input; an fp32
-                    # activation is only materialised where something else reads it
-                    coeffs = conv_same.conv.style_coefficients(latent[:, i + 1])
-                    split = conv_up.forward_split(src, latent[:, i], noise[2 * block - 1], coeffs[1],
-                                                  coeffs=up_coeffs if isinstance(src, M.SplitActivation) else None)
-                    rgb = to_rgb.coefficients(rgb_style) if M.torgb_fusable(cmid, csame, h2, w2) else None
-                    nb = block + 1
-                    is_last = block == self.log_size - 2
-                    s_up = None
-                    if not is_last and nb <= end_layer:
-                        nup, nsame = self.convs[2 * nb - 2], self.convs[2 * nb - 1]
-                        if (csame % 16 == 0 and M.modconv3x3_up_f16_supported(csame, nup.conv.out_channel, h2, w2, batch=nb_)
-                                and nup.conv.out_channel % 16 == 0
-                                and M.modconv3x3_f16_supported(nup.conv.out_channel, nsame.conv.out_channel, 2 * h2, 2 * w2, batch=nb_)
-                                and not _observed(nup, nsame)):
-                            up_coeffs = nup.conv.style_coefficients(latent[:, i + 2])
-                            s_up = up_coeffs[1]
-                    fused_rgb = rgb is not None and not _observed(to_rgb)
-                    # fp32 activation: read by a stand-alone ToRGB, returned on an early exit, or fed
-                    # to the next block as a plain tensor
-                    want_out = not fused_rgb or (not is_last and s_up is None)
-                    if (fused_rgb and not want_out and s_up is None and skip is not None and M.image_fusable(cmid, csame, h2, w2)
-                            and conv_same.activate.bias is not None):
-                        # the last layer: its epilogue finishes ToRGB (bias + upsampled skip) - no raw product, no finishing launch
-                        image = conv_same.forward_image(split, coeffs, noise[2 * block], rgb, to_rgb, skip)
-                        if image is not None:
-                            out, split_in, skip = None, None, image
-                            i += 2
-                            continue
-                    out, raw, split_in = conv_same.forward_from_split(split, coeffs, noise[2 * block],
-                                                                      rgb=rgb if fused_rgb else None, want_out=want_out,
-                                                                      split_for=s_up)
+                assert not isinstance(src, M.SplitActivation)  # a split is only produced for a fast block
+                split_in = None
+                out = conv_up(src, latent[:, i], noise=noise[2 * block - 1])
+                if fuses and not _observed(conv_same, to_rgb):  # ToRGB's 1x1 conv in the epilogue: the raw product travels
+                    # as an explicit value from the producing conv to its ToRGB
+                    out, raw = conv_same.forward_rgb(out, latent[:, i + 1], noise[2 * block], to_rgb.coefficients(latent[:, i + 2]))
+                    skip = to_rgb.finish(raw, skip)
                 else:
-                    assert not isinstance(src, M.SplitActivation)  # a split is only produced for a fast block
-                    split_in = raw = None
-                    out = conv_up(src, latent[:, i], noise=noise[2 * block - 1])
-                    if conv_same.conv.fuses_torgb(out) and not _observed(conv_same, to_rgb):  # ToRGB's 1x1 conv in the epilogue
-                        out, raw = conv_same.forward_rgb(out, latent[:, i + 1], noise[2 * block], to_rgb.coefficients(rgb_style))
-                    else:
-                        out = conv_same(out, latent[:, i + 1], noise=noise[2 * block])
-                # the raw 1x1 product travels as an explicit value from the producing conv to its ToRGB
-                skip = to_rgb.finish(raw, skip) if raw is not None else to_rgb(out, rgb_style, skip)
-            i += 2
+                    out = conv_same(out, latent[:, i + 1], noise=noise[2 * block])
+                    skip = to_rgb(out, latent[:, i + 2], skip)
         image = skip
         return (image, latent) if return_latents else (image, None)

@@ -456,7 +456,7 @@ def test_generator1024_fuses_torgb_of_the_top_layers(monkeypatch):
     lat, nz, _ = C.generator_inputs(size, 2, 0)  # batch 2: the smallest batch whose 32^2 layers take the fp16-core kernels
     lat, nz = lat.to(dev), [n.to(dev) for n in nz]
     fused, plain_rgb, presplit = [], [], []
-    real_conv, real_rgb, real_pre = M.modconv3x3_f16, M.torgb, M.modconv3x3_f16_pre
+    real_conv, real_rgb, real_pre = M.modconv3x3_f16, M.torgb, M._modconv3x3_f16_pre  # (the fixed-triple form the generator calls)
 
     def conv(*a, **k):
         if k.get("rgb") is not None:
@@ -469,7 +469,7 @@ def test_generator1024_fuses_torgb_of_the_top_layers(monkeypatch):
             fused.append(a[2].shape[2])
         return real_pre(*a, **k)
 
-    monkeypatch.setattr(M, "modconv3x3_f16_pre", pre)
+    monkeypatch.setattr(M, "_modconv3x3_f16_pre", pre)
     image, real_image = [], M.modconv3x3_f16_pre_image
 
     def pre_image(*a, **k):  # round 6: the last layer's epilogue finishes ToRGB (no raw product, no finishing launch)
@@ -510,10 +510,10 @@ def test_generator1024_fuses_torgb_of_the_top_layers(monkeypatch):
         # finishing passes on the raw slabs (8, 4, 2, 1, 1 slabs of 3 channels); the layers below 64^2 run the stand-alone ToRGB
         assert plain_rgb == [512, 512, 512, 512, 24, 12, 6, 3], plain_rgb
         # ... and the two-launch form of the last layer (HAIRFAST_IMAGE_FUSE=0) gives the same image, bit for bit
-        monkeypatch.setenv("HAIRFAST_IMAGE_FUSE", "0")
         image.clear()
-        y2, _ = g([lat], input_is_latent=True, noise=nz)
-        monkeypatch.delenv("HAIRFAST_IMAGE_FUSE")
+        with monkeypatch.context() as two_launch:
+            two_launch.setattr(M, "IMAGE_FUSE", False)
+            y2, _ = g([lat], input_is_latent=True, noise=nz)
         assert image == [] and torch.equal(y, y2)
         # batch 1 under batch-invariant plans (the default): the kernel families of the canonical batch-3 launch - the same chain
         fused.clear(); presplit.clear(); up_pre.clear(); up_fused.clear(); plain_rgb.clear()
