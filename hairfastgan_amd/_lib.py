@@ -68,6 +68,13 @@ SIGNATURES = {
     "hf_poisson_setup_u8": [_f, _f, _f, _f, _f, _i, _i, _i, _i, _st],
     "hf_poisson_jacobi_f32": [_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _st],
     "hf_poisson_finish_u8": [_f, _f, _f, _f, _i, _i, _i, _i, _st],
+    "hf_resize_lanczos_u8": [_f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _i, _f, _f, _i, _st],
+    "hf_quad_bilinear_u8": [_f, _f, ctypes.POINTER(ctypes.c_double), _i, _i, _i, _i, _i, _st],
+    "hf_quad_lanczos4_u8": [_f, _f, ctypes.POINTER(ctypes.c_double), _i, _i, _i, _i, _f, _f, _i, _st],
+    "hf_quad_lanczos4_ratio": [],
+    "hf_align_pad_blur_f32": [_f, _f, _f, _f, _i, _f, _f, _i, _i, _i, _i, _i, _i, _i, _st],
+    "hf_align_pad_finish_u8": [_f, _f, _f, _f, _f, _f, _i, _i, _i, _st],
+    "hf_u8_to_unit_f32": [_f, _f, _ll, _st],
     "hf_maxpool3x3s2_f32": [_f, _f, _ll, _i, _i, _st],
     "hf_gate_f32": [_f, _f, _f, _f, _f, _fl, _ll, _i, _st],
     "hf_upsample_nearest_f32": [_f, _f, _ll, _i, _i, _i, _i, _st],

@@ -1307,3 +1307,109 @@ def poisson_finish(lib, st, x, tgt, mask):
     out = torch.empty_like(tgt)
     check(lib, lib.hf_poisson_finish_u8(_p(out), _p(x), _p(tgt), _p(mask), n, c, h, w, st), "hf_poisson_finish_u8")
     return out
+
+
+# ---- FFHQ face alignment (csrc/align.h; hairfastgan_amd.face_align chains these).  Images: planar uint8 [C,H,W] ----
+def _planes(img):
+    img = _u8(img)
+    if img.ndim != 3:
+        raise ValueError(f"expected a planar uint8 image [C,H,W]; got {tuple(img.shape)}")
+    return img
+
+
+def _table(pair):
+    """(bounds int32 [n,2], kk int32 [n,ksize]) of one Lanczos pass, or None -> (pointers, ksize)."""
+    if pair is None:
+        return None, None, 0
+    bounds, kk = pair
+    if bounds.dtype != torch.int32 or kk.dtype != torch.int32 or bounds.ndim != 2 or bounds.shape[1] != 2 or kk.ndim != 2 \
+            or kk.shape[0] != bounds.shape[0] or not bounds.is_contiguous() or not kk.is_contiguous():
+        raise ValueError("a Lanczos table is (bounds int32 [n,2], kk int32 [n,ksize]), contiguous")
+    return bounds, kk, kk.shape[1]
+
+
+def _coef8(coef):
+    import ctypes
+
+    if len(coef) != 8:
+        raise ValueError("the quad transform takes 8 coefficients a0..a7")
+    return (ctypes.c_double * 8)(*[float(v) for v in coef])
+
+
+def resize_lanczos_u8(lib, st, img, out_h, out_w, table_x, table_y):
+    """PIL's 8-bit Lanczos resize: table_x / table_y = face_align.lanczos_coeffs of the axis on the device (None for an
+    axis whose size does not change)."""
+    img = _planes(img)
+    c, h, w = img.shape
+    bx, kx, nx = _table(table_x)
+    by, ky, ny = _table(table_y)
+    if (bx is None) != (out_w == w) or (by is None) != (out_h == h) or (bx is not None and bx.shape[0] != out_w) \
+            or (by is not None and by.shape[0] != out_h):
+        raise ValueError("one table per axis whose size changes, with one row per output sample")
+    out = torch.empty((c, out_h, out_w), dtype=torch.uint8, device=img.device)
+    mid = torch.empty((c, h, out_w), dtype=torch.uint8, device=img.device) if bx is not None and by is not None else None
+    check(lib, lib.hf_resize_lanczos_u8(_p(out), _p(mid), _p(img), c, h, w, out_h, out_w, _p(bx), _p(kx), nx, _p(by), _p(ky), ny, st),
+          "hf_resize_lanczos_u8")
+    return out
+
+
+def quad_bilinear_u8(lib, st, img, coef, out_h, out_w):
+    """PIL's transform(QUAD, BILINEAR) with the coefficients a0..a7 of face_align.quad_coefficients."""
+    img = _planes(img)
+    c, h, w = img.shape
+    out = torch.empty((c, out_h, out_w), dtype=torch.uint8, device=img.device)
+    check(lib, lib.hf_quad_bilinear_u8(_p(out), _p(img), _coef8(coef), c, h, w, out_h, out_w, st), "hf_quad_bilinear_u8")
+    return out
+
+
+def quad_lanczos4_u8(lib, st, img, coef, out_size, table):
+    """quad_bilinear_u8 to (4 out_size)^2 and resize_lanczos_u8 to out_size^2 in one launch; table = the 4 out_size ->
+    out_size pass."""
+    img = _planes(img)
+    c, h, w = img.shape
+    b, k, n = _table(table)
+    if b is None or b.shape[0] != out_size:
+        raise ValueError("the table must have one row per output sample")
+    out = torch.empty((c, out_size, out_size), dtype=torch.uint8, device=img.device)
+    check(lib, lib.hf_quad_lanczos4_u8(_p(out), _p(img), _coef8(coef), c, h, w, out_size, _p(b), _p(k), n, st), "hf_quad_lanczos4_u8")
+    return out
+
+
+def align_pad_blur(lib, st, img, weights, radius, mask_x, mask_y, pad):
+    """Reflect pad by pad = (left, top, right, bottom), Gaussian (2 radius + 1 float64 weights) and the blur fade -> fp32
+    [C,H,W]; mask_x fp32 [W], mask_y fp32 [H]."""
+    img = _planes(img)
+    c, h, w = img.shape
+    left, top, right, bottom = (int(v) for v in pad)
+    H, W = h + top + bottom, w + left + right
+    if weights.dtype != torch.float64 or weights.numel() != 2 * radius + 1 or not weights.is_contiguous():
+        raise ValueError("weights: 2 * radius + 1 contiguous float64 values")
+    mask_x, mask_y = _c(mask_x), _c(mask_y)
+    if mask_x.numel() != W or mask_y.numel() != H:
+        raise ValueError(f"mask_x / mask_y must have {W} / {H} elements")
+    out = torch.empty((c, H, W), dtype=torch.float32, device=img.device)
+    tmp = torch.empty_like(out)
+    check(lib, lib.hf_align_pad_blur_f32(_p(out), _p(tmp), _p(img), _p(weights), radius, _p(mask_x), _p(mask_y), c, h, w, left, top,
+                                         right, bottom, st), "hf_align_pad_blur_f32")
+    return out
+
+
+def align_pad_finish(lib, st, img, median, mask_x, mask_y, return_float=False):
+    """The median fade, rint, clip -> (uint8 [C,H,W], the fp32 image before rint or None)."""
+    img, median, mask_x, mask_y = _c(img), _c(median), _c(mask_x), _c(mask_y)
+    c, h, w = img.shape
+    if median.numel() != c or mask_x.numel() != w or mask_y.numel() != h:
+        raise ValueError("median [C], mask_x [W] and mask_y [H] must match the image")
+    out = torch.empty((c, h, w), dtype=torch.uint8, device=img.device)
+    pre = torch.empty_like(img) if return_float else None
+    check(lib, lib.hf_align_pad_finish_u8(_p(out), _p(pre), _p(img), _p(median), _p(mask_x), _p(mask_y), c, h, w, st),
+          "hf_align_pad_finish_u8")
+    return out, pre
+
+
+def u8_to_unit(lib, st, img):
+    """float32 byte / 255 (ToTensor)."""
+    img = _u8(img)
+    out = torch.empty(img.shape, dtype=torch.float32, device=img.device)
+    check(lib, lib.hf_u8_to_unit_f32(_p(out), _p(img), img.numel(), st), "hf_u8_to_unit_f32")
+    return out

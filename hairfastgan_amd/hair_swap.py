@@ -719,6 +719,9 @@ class HairFast:
       batch_invariant this object's plan mode (None: the process-wide HAIRFAST_DETERMINISTIC / set_batch_invariant, ON by
                       default): True = `swap_batch` gives every triple the bits - and mask indices - `swap` gives it alone;
                       False = plans from the whole launch (a few per cent faster batched, near-tie argmax flips possible)
+      landmark_detector  `swap(..., align=True)`: a callable image (uint8 HWC numpy array) -> [68,2] landmarks of the face to
+                      align on - the reference's dlib detector + 68-point predictor (utils/shape_predictor.py:49-77;
+                      INTEGRATION.md); the alignment itself runs natively (hairfastgan_amd.face_align)
       sean_state + sean_mean_codes   SEAN generator (…/CelebA-HQ_pretrained/latest_net_G.pth) and the [19,512] per-label
                       median style codes (models/sean_codes/styles_test/mean_style_code/median/<label>/ACE.npy)
     """
@@ -751,8 +754,9 @@ class HairFast:
     def __init__(self, args, *, stages=None, generator_state=None, e4e_state=None, fs_state=None, e4e_latent_avg=None,
                  fs_dlatent_avg=None, pp_state=None, pp_latent_avg=None, bisenet_state=None, rotate_state=None,
                  blend_state=None, clip_image_embed=None, shape_state=None, sean_state=None, sean_mean_codes=None,
-                 clip_state=None, pretrained_root=None, conv_precision=None, batch_invariant=None):
+                 clip_state=None, pretrained_root=None, conv_precision=None, batch_invariant=None, landmark_detector=None):
         self.args = args
+        self.landmark_detector = landmark_detector  # swap(align=True): image (uint8 HWC array) -> [68,2] landmarks
         self.conv_precision = conv_precision  # None: the process-wide mode; else this object's own (set per call)
         self.batch_invariant = batch_invariant  # None: the process-wide setting (default on); True / False: this object's own
         conv_precision_scope(conv_precision)  # validates
@@ -817,9 +821,28 @@ class HairFast:
         return self.blend.blend_images_batch(aligns_shape, aligns_color, name_to_embed,
                                              [tuple(key(t, n) for n in ("face", "shape", "color")) for t in range(T)], **kwargs)
 
-    def swap(self, face_img, shape_img, color_img, benchmark=False, align=False, seed=None, exp_name=None, **kwargs):
+    def _align_images(self, images, landmarks):
+        """hair_swap.py:93-94: `align_face(images)` with the landmarks from `landmarks` (arrays or a callable) or this
+        object's `landmark_detector`; NotImplementedError without either - the detector is dlib's, not part of this backend."""
+        from . import face_align as FA
+
+        source = landmarks if landmarks is not None else self.landmark_detector
+        if source is None:
+            raise NotImplementedError(
+                "align=True needs 68-point face landmarks: pass landmarks=[face, shape, color] arrays of [68,2] or construct "
+                "HairFast(..., landmark_detector=callable) - the reference's dlib detector and shape predictor "
+                "(utils/shape_predictor.py:49-77) are a third-party model outside this backend (INTEGRATION.md)")
+        images = [FA.to_bytes(im, self.args.device) for im in images]
+        return FA.align_face(images, FA.landmarks_for(images, source))
+
+    def swap(self, face_img, shape_img, color_img, benchmark=False, align=False, seed=None, exp_name=None, landmarks=None,
+             **kwargs):
         """hair_swap.py:63-103.  Images: torch.Tensor [3,H,W] (uint8 or float in [0,1]), `PIL.Image.Image`, numpy HWC
         arrays, or file paths (image files decoded through PIL like the reference's `read_image(..., RGB)`; `.npy` arrays).
+
+        align=True: arbitrary photographs - each image is first cropped to its face the FFHQ way (hairfastgan_amd.face_align)
+        from `landmarks` (three [68,2] arrays, or a callable image (uint8 HWC array) -> [68,2]; default: this object's
+        `landmark_detector`), and the return is (final, face, shape, color) with the aligned images, as in the reference.
 
         Randomness: `seed` (default 3407, utils/seed.py:19) makes a swap reproducible on THIS backend; it does not
         reproduce a seeded run of the reference sample for sample: the per-layer noise of a generator forward is one draw
@@ -832,7 +855,7 @@ class HairFast:
         cache = {}
         images = [self._as_tensor(img, cache) for img in (face_img, shape_img, color_img)]
         if align:
-            raise NotImplementedError("align=True needs the reference's dlib face aligner (utils/shape_predictor.py): out of scope")
+            images = self._align_images(images, landmarks)
         images = equal_replacer(images)
         set_seed(3407 if seed is None else seed)  # utils/seed.py:19-31
         if benchmark:  # utils/time.py:15-37
@@ -851,6 +874,8 @@ class HairFast:
             self._times.append(time.time() - t0)
             print(f"\n{len(self._times)} experiment ended in {self._times[-1]:.3f}(s)\nmin time: {np.min(self._times):.3f}(s), "
                   f"median time: {np.median(self._times):.3f}(s), std time: {np.std(self._times):.3f}(s)", file=sys.stderr)
+        if align:
+            return (final_image, *images)
         return final_image
 
     __call__ = swap
@@ -882,13 +907,23 @@ class HairFast:
         set_seed(3407 if seed is None else seed)
         return graphs[key](*images).clone()  # (the key carries the mode the graph was captured in)
 
-    def swap_batch(self, triples, seed=None, **kwargs):
+    def swap_batch(self, triples, seed=None, align=False, landmarks=None, **kwargs):
         """Several swaps as ONE batched pass over the hot path (not in the reference: BASELINE.json configs[3],
         "batched HairFast swap").  triples: sequence of (face, shape, color) with the image forms `swap` takes
         (tensors / arrays).  Returns a list of [3, size, size] images in [0, 1], one per triple, equal to what
-        `swap` returns for each triple given the same per-layer noise."""
+        `swap` returns for each triple given the same per-layer noise.  align=True: as in `swap`; `landmarks` is one
+        triple of [68,2] arrays per triple of images (or a callable), and every entry of the returned list is
+        (final, face, shape, color)."""
         cache = {}
-        prepared = equal_replacer_many([[self._as_tensor(img, cache) for img in triple] for triple in triples])
+        tensors = [[self._as_tensor(img, cache) for img in triple] for triple in triples]
+        if align:
+            if landmarks is not None and not callable(landmarks):
+                landmarks = list(landmarks)
+                if len(landmarks) != len(tensors):
+                    raise ValueError(f"landmarks: one triple of [68,2] arrays per triple of images ({len(tensors)}); got {len(landmarks)}")
+            tensors = [self._align_images(tr, landmarks if landmarks is None or callable(landmarks) else landmarks[t])
+                       for t, tr in enumerate(tensors)]
+        prepared = equal_replacer_many(tensors)
         set_seed(3407 if seed is None else seed)
         # a triple that repeats an image takes the reference's shortcuts (no mixing / no second Rotate): one by one
         plain = [t for t, tr in enumerate(prepared) if len({id(x) for x in tr}) == 3]
@@ -907,7 +942,10 @@ class HairFast:
             return res
 
         with conv_precision_scope(self.conv_precision), batch_invariant_scope(self.batch_invariant):
-            return run_guarded(run)
+            finals = run_guarded(run)
+        if align:
+            return [(final, *tr) for final, tr in zip(finals, prepared)]
+        return finals
 
     def poisson_image_blending(self, final_image, face_img, dilate_erosion=30, maxn=115):
         """utils/image_utils.py:58-94 with this object's BiSeNet: pastes the non-hair region of `face_img` (the image forms

@@ -549,6 +549,41 @@ int hf_poisson_jacobi_f32(float *x_out, const float *x_in, const float *b, const
 int hf_poisson_finish_u8(unsigned char *out, const float *x, const unsigned char *tgt, const unsigned char *mask, int images,
                          int channels, int h, int w, void *stream);
 
+/* ---- FFHQ face alignment from landmarks (utils/shape_predictor.py:145-185: PIL + scipy; csrc/align.h) ----
+ * Every image is planar u8 [planes, h, w].  Tables and weights are device arrays computed by the host in double
+ * (hairfastgan_amd/face_align.py: lanczos_coeffs, quad_coefficients, gaussian_weights).
+ *
+ * PIL Image.resize((w_out, h_out), LANCZOS): horizontal pass in -> mid [planes, h_in, w_out] (rounded to bytes), vertical
+ * pass mid -> out [planes, h_out, w_out].  A pass whose size does not change is skipped (its tables may be null; `mid` is
+ * only needed when both run).  bounds_* int32 [n_out, 2] = (first tap, tap count), kk_* int32 [n_out, ksize] 22-bit
+ * fixed-point weights; byte = clamp((2^21 + sum pixel * k) >> 22, 0, 255).  HF_E_INVALID if neither size changes. */
+int hf_resize_lanczos_u8(unsigned char *out, unsigned char *mid, const unsigned char *in, int planes, int h_in, int w_in,
+                         int h_out, int w_out, const int *bounds_x, const int *kk_x, int ksize_x, const int *bounds_y,
+                         const int *kk_y, int ksize_y, void *stream);
+/* PIL Image.transform((ow, oh), QUAD, quad, BILINEAR): coef8 = HOST pointer to a0..a7 of xin = a0 + a1 x + a2 y + a3 x y,
+ * yin = a4 + ... at (x + 0.5, y + 0.5); 0 outside [0, w) x [0, h); lerps in double, truncated.  out [planes, oh, ow]. */
+int hf_quad_bilinear_u8(unsigned char *out, const unsigned char *src, const double *coef8, int planes, int h, int w, int oh,
+                        int ow, void *stream);
+/* hf_quad_bilinear_u8 to (R*osize)^2 followed by hf_resize_lanczos_u8 to osize^2 in one launch, R = hf_quad_lanczos4_ratio()
+ * = 4; the intermediate lives in LDS.  bounds / kk: the tables of the R*osize -> osize pass.  Same bytes as the pair. */
+int hf_quad_lanczos4_u8(unsigned char *out, const unsigned char *src, const double *coef8, int planes, int h, int w, int osize,
+                        const int *bounds, const int *kk, int ksize, void *stream);
+int hf_quad_lanczos4_ratio(void);
+/* shape_predictor.py:170-176 on src [planes, h, w]: img = np.pad(float32(src), reflect); out = img + (gaussian_filter(img) -
+ * img) * clip(mask * 3 + 1, 0, 1), fp32 [planes, H, W], H = pad_top + h + pad_bottom, W = pad_left + w + pad_right.
+ * weights: 2*radius+1 doubles (normalised); the filter runs along H first, each axis accumulates in double and is stored
+ * as fp32 (tmp: fp32 scratch of out's size); mask = max(mask_x[x], mask_y[y]), fp32 [W] / [H].
+ * HF_E_INVALID if radius >= H or radius >= W or radius > 448 (the LDS strip). */
+int hf_align_pad_blur_f32(float *out, float *tmp, const unsigned char *src, const double *weights, int radius,
+                          const float *mask_x, const float *mask_y, int planes, int h, int w, int pad_left, int pad_top,
+                          int pad_right, int pad_bottom, void *stream);
+/* shape_predictor.py:177-178: v = img + (median[plane] - img) * clip(mask, 0, 1) (fp32); pre (may be null) = v;
+ * out = uint8(clip(rint(v), 0, 255)).  img / pre fp32, out u8 [planes, h, w]; median fp32 [planes]. */
+int hf_align_pad_finish_u8(unsigned char *out, float *pre, const float *img, const float *median, const float *mask_x,
+                           const float *mask_y, int planes, int h, int w, void *stream);
+/* torchvision ToTensor on bytes: out = float(in) / 255 (a correctly rounded division, not a reciprocal multiply) */
+int hf_u8_to_unit_f32(float *out, const unsigned char *in, long long n, void *stream);
+
 /* ---- PostProcessModel's latent branch (models/Encoders.py:13-32, 119-131) ----
  * F.layer_norm over the last `dim` elements of each of `rows` rows (biased variance, eps inside the sqrt):
  * gamma / beta [dim] = elementwise affine (both NULL: LayerNorm(elementwise_affine=False), :19), lrelu != 0
