@@ -1,6 +1,8 @@
 // conv_common.h - declarations shared by the convolution kernels (modconv.hip: exact-fp32
 // MFMA; convh.hip: fp16-split MFMA): launch parameters, tile geometry, the epilogue.
 #pragma once
+#include <type_traits>
+
 #include "hf_common.h"
 
 namespace hf_detail {
@@ -52,10 +54,10 @@ struct ConvParams {
   long long zslab;             // split-K: floats per z slab of `partial` (= groups*batch*cout*oh*ow)
   int splits;                  // split-K: blockIdx.z handles chunks [z*cps, (z+1)*cps); 1 = off
   int chunks_per_split;
-  int swap_xy;                 // convh_enc.hip: the grid is (columns, tiles) instead of (tiles, columns) - blocks are dispatched
-                               // x-fastest, so consecutive blocks then share an INPUT tile and walk the (group, channel-tile)
+  int swap_xy;                 // convh.hip, convh_enc.hip: the grid is (columns, tiles) instead of (tiles, columns) - blocks are
+                               // dispatched x-fastest, so consecutive blocks then share an INPUT tile and walk the (group, channel-tile)
                                // columns: the input tile stays in L2 while the weights stream from the Infinity Cache
-                               // (run_enc picks the order with the smaller beyond-L2 traffic)
+                               // (columns_fastest below: the order with the smaller beyond-L2 traffic)
   int persist;                 // convh_enc.hip (conv_enc_h): the launch is `persist` resident blocks that walk the (lin_x x lin_y) block
   int lin_x, lin_y;            // grid of the plain form in dispatch order, block b taking b, b + persist, ... (0 = one block per tile)
   int vsplit;                  // "virtual" split-K (convh_enc.hip, gemm_h.hip; batch-invariant plans): the K partition into `splits`
@@ -445,6 +447,40 @@ __device__ __forceinline__ void store_tile_rows(const ConvParams &P, const TileG
   }
 }
 
+// ---- launch-side decisions stated once -----------------------------------------------------------------
+
+// LDS carve-up of the fp16 3x3 kernels (conv_mfma_h, conv_enc_h, conv_enc_s2mt_h) in 16-byte units, for the kernel to carve
+// and its launcher to allocate: two stage buffers [W hi][W lo][X hi][X lo] (lo: f16x3 only), then the kernel's fp32 tables.
+// MIN_UNITS: a stage buffer that doubles as something larger (conv_mfma_h FUSE: the epilogue's vertical exchange).
+template <int NTERMS, int CT, int NPIX_, int MIN_UNITS = 0>
+struct StageLayout {
+  static constexpr int NPIX = NPIX_;
+  static constexpr int NPART = (NTERMS == 3) ? 2 : 1;  // hi (+ lo)
+  static constexpr int W_UNITS = 9 * 2 * CT;           // 16-byte units of one weight part per stage
+  static constexpr int X_UNITS = 2 * NPIX;             // 16-byte units of one activation part per stage
+  static constexpr int BUF_UNITS = NPART * (W_UNITS + X_UNITS) < MIN_UNITS ? MIN_UNITS : NPART * (W_UNITS + X_UNITS);
+  static constexpr int OFF_WL = W_UNITS, OFF_XH = NPART * W_UNITS, OFF_XL = NPART * W_UNITS + X_UNITS;
+  static constexpr size_t stage_bytes = (size_t)2 * BUF_UNITS * 16;
+  // floats of the [2][cin] per-input-channel table behind the stages (rows padded to 16 bytes)
+  __host__ __device__ static constexpr int cin_table_floats(int cin) { return 2 * ((cin + 3) & ~3); }
+};
+
+// The generator's standard StyledConv tail - noise + bias + leaky ReLU with 0 <= alpha <= 1, * scale > 0: conv_mfma_h's
+// straight-line epilogue (fast_ep), which is also the one that writes a fused ToRGB in several slabs (launch_h).
+// (A macro, not a function: through an inlined function - P by reference or its four fields by value - hipcc compiles every
+// same-resolution conv_mfma_h differently, tools/compare_isa.sh; the text below is the kernel's own expression.)
+#define HF_STD_STYLED_TAIL(P) ((P).bias && (P).act == ACT_LRELU && (P).alpha >= 0.0f && (P).alpha <= 1.0f && (P).scale > 0.0f)
+
+// a run-time flag / operand mode as a compile-time constant handed to a generic lambda
+template <class F>
+auto with_bool(bool v, F &&f) {
+  return v ? f(std::true_type{}) : f(std::false_type{});
+}
+template <class F>
+auto with_nterms(int nterms, F &&f) {
+  return nterms == 3 ? f(std::integral_constant<int, 3>{}) : f(std::integral_constant<int, 1>{});
+}
+
 inline int ilog2(int v) {
   int l = 0;
   while ((1 << (l + 1)) <= v) ++l;
@@ -513,5 +549,19 @@ int launch_splitk_reduce(ConvParams &P, bool with_epilogue, hipStream_t st);
 // the registered arrival-counter buffer (hf_set_splitk_counters) when it can hold one counter per output tile
 // (grid.x * grid.y) of this launch, else NULL (= the splitk_reduce launch)
 unsigned int *splitk_counters_for(long long tiles);
+
+// Block order of a (tiles x columns) launch, column = (group, output-channel tile); blocks are dispatched x-fastest, 256 at a
+// time.  Tiles-fastest keeps a column's weights in L2 and re-reads every input tile once per column from beyond L2 (columns x
+// col_in); columns-fastest keeps ~256 / columns input tiles in L2 and re-reads the weights once per such group (they fit the
+// 256 MB Infinity Cache; the input of a batched pass does not).  True = columns fastest moves fewer bytes from beyond L2.
+// in_bytes = all inputs once (= col_in unless groups have their own).  (An input that fits the Infinity Cache beside the rest is
+// re-read from there either way: measured neutral at batch 8 - tools/probes/gen_layers.py, r05j - so only from half of it upward,
+// i.e. in the batched swap's encoder and generator calls; hf_debug_set_tuning bit 3: tests force the order.)
+inline bool columns_fastest(double col_in, double in_bytes, double w_bytes, int columns, int tiles) {
+  const double tiles_fast = (double)columns * col_in + w_bytes;
+  const double resident = columns >= 256 ? 1.0 : 256.0 / columns;  // input tiles in flight at a time
+  const double cols_fast = in_bytes + w_bytes * ((double)tiles / resident);
+  return (g_h_tune & 8) || (col_in > 128e6 && cols_fast < 0.5 * tiles_fast);
+}
 
 }  // namespace hf_detail

@@ -118,26 +118,36 @@ __host__ __device__ constexpr int group_first(int g) {  // first position of gro
   return !UP ? g : (g == 0 ? 0 : g == 1 ? 4 : g == 2 ? 6 : g == 3 ? 8 : 9);
 }
 
+// Tile shape and LDS carve-up of conv_mfma_h, shared with launch_h: the stages (StageLayout, conv_common.h), then
+// [2][cin] s of the current / next image, [2][3][CT] epilogue tables (d, bias, s_next) and - fused ToRGB - [2][3][CT] weights.
+template <int NTERMS, int CT_TILES, int PG, int WAVES_CO, int WAVES_PX, bool UP, int TWMAX, bool FUSE>
+struct HShape {
+  static constexpr int NW = WAVES_CO * WAVES_PX;
+  static constexpr int NT = 64 * NW;
+  static constexpr int CT = 32 * CT_TILES * WAVES_CO;
+  static constexpr int PT = 32 * PG * WAVES_PX;  // pixels (UP: phase-domain positions) per tile
+  // FUSE: the epilogue's vertical exchange (NW * XSLOTS slots of 64 lanes x 16 B) lives in the free stage buffer - with plain
+  // fp16 operands (one part) a stage is smaller than that, the buffer is sized for the exchange
+  // (one row per wave, PG == 1: the row's four phases once - 4 slots; two rows per wave: the upper row's four + the lower row's two)
+  static constexpr int XSLOTS = (PG == 1) ? 4 : 6;
+  using Stage = StageLayout<NTERMS, CT, halo_pixels_max<PT, UP, TWMAX, FUSE>(), FUSE ? NW * XSLOTS * 64 : 0>;
+  static constexpr int TABLE_FLOATS = 2 * 3 * CT;
+  static size_t lds_bytes(int cin, bool rgb) {
+    return Stage::stage_bytes + (Stage::cin_table_floats(cin) + (rgb ? 2 : 1) * TABLE_FLOATS) * sizeof(float);
+  }
+};
+
 // (second launch bound = waves per SIMD the register allocation must admit: a 16-wave block is four per SIMD, 128 registers)
 template <int NTERMS, int CT_TILES, int PG, int WAVES_CO, int WAVES_PX, bool MOD, bool UP, int TWMAX, bool PRE, bool FUSE = false>
 __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 16 ? 4 : 2)) void conv_mfma_h(const ConvParams P,
                                                                           const _Float16 *__restrict__ wth,
                                                                           const _Float16 *__restrict__ wtl) {
-  constexpr int NW = WAVES_CO * WAVES_PX;
-  constexpr int NT = 64 * NW;
-  constexpr int CT = 32 * CT_TILES * WAVES_CO;
-  constexpr int PT = 32 * PG * WAVES_PX;  // pixels (UP: phase-domain positions) per tile
+  using S = HShape<NTERMS, CT_TILES, PG, WAVES_CO, WAVES_PX, UP, TWMAX, FUSE>;
+  using L = typename S::Stage;
+  constexpr int NW = S::NW, NT = S::NT, CT = S::CT, PT = S::PT, XSLOTS = S::XSLOTS;
   constexpr int NPH = UP ? 4 : 1;
   constexpr int HALO = UP ? 1 : 2;
-  constexpr int NPIX = halo_pixels_max<PT, UP, TWMAX, FUSE>();
-  constexpr int NPART = (NTERMS == 3) ? 2 : 1;          // hi (+ lo)
-  constexpr int W_UNITS = 9 * 2 * CT;                   // 16-byte units of one weight part per stage
-  constexpr int X_UNITS = 2 * NPIX;                     // 16-byte units of one activation part per stage
-  // FUSE: the epilogue's vertical exchange (NW * 6 slots of 64 lanes x 16 B) lives in the free stage buffer - with plain
-  // fp16 operands (one part) a stage is smaller than that, the buffer is sized for the exchange
-  // (one row per wave, PG == 1: the row's four phases once - 4 slots; two rows per wave: the upper row's four + the lower row's two)
-  constexpr int XSLOTS = (PG == 1) ? 4 : 6;
-  constexpr int BUF_UNITS = (FUSE && NPART * (W_UNITS + X_UNITS) < NW * XSLOTS * 64) ? NW * XSLOTS * 64 : NPART * (W_UNITS + X_UNITS);
+  constexpr int NPIX = L::NPIX, NPART = L::NPART, W_UNITS = L::W_UNITS, X_UNITS = L::X_UNITS, BUF_UNITS = L::BUF_UNITS;
   constexpr int N_WPIECE = NPART * W_UNITS / 64;        // 1 KiB DMA pieces per stage
   constexpr bool PP = PRE && NW == 8;                   // the ping-pong K loop (below)
   constexpr int ND = (N_WPIECE + NW - 1) / NW;          // per wave
@@ -154,7 +164,7 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
   HF_DYN_LDS;
   half8 *lds = reinterpret_cast<half8 *>(hf_dyn_lds);               // [2][BUF_UNITS] 16-byte units
   // buffer layout (units): [W hi][W lo][X hi][X lo]
-  constexpr int OFF_WL = W_UNITS, OFF_XH = NPART * W_UNITS, OFF_XL = NPART * W_UNITS + X_UNITS;
+  constexpr int OFF_WL = L::OFF_WL, OFF_XH = L::OFF_XH, OFF_XL = L::OFF_XL;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -179,8 +189,8 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
   // In LDS so that the epilogue issues NO vector-memory loads: on gfx9 loads and stores share
   // vmcnt, every load that follows a store waits for that store's acknowledgement (measured:
   // the epilogue's second pixel group waited ~12k cycles behind the first group's stores).
-  float *ep_base = sl_base + 2 * ((P.cin + 3) & ~3);
-  float *rgbw_base = ep_base + 2 * 3 * CT;  // fused ToRGB: [2 slots][3][CT] = rgb_w[co][c] * rgb_s[b][co]
+  float *ep_base = sl_base + L::cin_table_floats(P.cin);
+  float *rgbw_base = ep_base + S::TABLE_FLOATS;  // fused ToRGB: [2 slots][3][CT] = rgb_w[co][c] * rgb_s[b][co]
 
   // ---- tiles: the block walks tiles blockIdx.x, +gridDim.x, ... of its cout tile as ONE
   // pipeline - the first stage of the next tile is prefetched during the last stage of the
@@ -245,7 +255,7 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
   //   scale * lrelu(acc*d + n + b) = max(o, alpha*o),  o = acc*(d*scale) + (n*scale + b*scale)
   // - d*scale and b*scale are folded into the per-image epilogue table below.  Anything else (no bias, other
   // activations) takes the general epilogue with its run-time switches.
-  const bool fast_ep = !UP && P.bias && P.act == ACT_LRELU && P.alpha >= 0.0f && P.alpha <= 1.0f && P.scale > 0.0f;
+  const bool fast_ep = !UP && HF_STD_STYLED_TAIL(P);
   const float ep_fold = (FUSE || fast_ep) ? P.scale : 1.0f;
   auto load_s = [&](int b, int slot) {
     float *dst = sl_base + slot * P.cin;
@@ -1059,11 +1069,8 @@ __global__ __launch_bounds__(256) void split_weights(_Float16 *__restrict__ wth,
 
 template <int NTERMS, int CT_TILES, int PG, int WAVES_CO, int WAVES_PX, bool UP, int TWMAX = 32, bool PRE = false, bool FUSE = false>
 int launch_h(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, hipStream_t st) {
-  constexpr int NT = 64 * WAVES_CO * WAVES_PX;
-  constexpr int CT = 32 * CT_TILES * WAVES_CO;
-  constexpr int PT = 32 * PG * WAVES_PX;
-  constexpr int NPIX = halo_pixels_max<PT, UP, TWMAX, FUSE>();
-  constexpr int NPART = (NTERMS == 3) ? 2 : 1;
+  using S = HShape<NTERMS, CT_TILES, PG, WAVES_CO, WAVES_PX, UP, TWMAX, FUSE>;
+  constexpr int NT = S::NT, CT = S::CT, PT = S::PT, NPIX = S::Stage::NPIX;
   if (P.cin % KH || P.cout % CT || P.stride != 1 || P.t || P.groups > 1 || P.residual || P.act == ACT_PRELU)
     return HF_E_INVALID;
   if ((long long)P.cin * P.h * P.w >= (1LL << 31)) return HF_E_INVALID;
@@ -1097,16 +1104,10 @@ int launch_h(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, hipStream_
     if (P.g[i].lg_nb != 0 || (1 << (P.g[i].lg_tw + P.g[i].lg_th)) != PT) return HF_E_INVALID;
     if (geom_xs(P.g[i], 1, UP ? 1 : 2) > NPIX) return HF_E_INVALID;
   }
-  constexpr int NW_ = WAVES_CO * WAVES_PX;
-  constexpr int XSLOTS = (PG == 1) ? 4 : 6;
-  constexpr int BUF_UNITS = (FUSE && NPART * (9 * 2 * CT + 2 * NPIX) < NW_ * XSLOTS * 64) ? NW_ * XSLOTS * 64 : NPART * (9 * 2 * CT + 2 * NPIX);
-  const size_t lds = (size_t)2 * BUF_UNITS * 16 + 2 * ((P.cin + 3) & ~3) * sizeof(float) +
-                     2 * 3 * CT * sizeof(float) + (P.rgb_out ? 2 * 3 * CT * sizeof(float) : 0);
-  // stages + s[2][cin] + epilogue d/bias/s_next [2][3][CT] (+ fused ToRGB weights [2][3][CT])
+  const size_t lds = S::lds_bytes(P.cin, P.rgb_out != nullptr);
   // fused ToRGB: the standard StyledConv tail (the kernel's fast epilogue) writes one raw slab per 32*CT_TILES output
   // channels; the general epilogue only handles the one-slab case
-  const bool std_tail = P.bias && P.act == ACT_LRELU && P.alpha >= 0.0f && P.alpha <= 1.0f && P.scale > 0.0f;
-  if (P.rgb_out && (UP || !P.rgb_w || !P.rgb_s || (!std_tail && (WAVES_CO != 1 || P.cout != CT)) ||
+  if (P.rgb_out && (UP || !P.rgb_w || !P.rgb_s || (!HF_STD_STYLED_TAIL(P) && (WAVES_CO != 1 || P.cout != CT)) ||
                     P.rgb_slabs != P.cout / (32 * CT_TILES)))
     return HF_E_INVALID;
   if (lds > 160 * 1024) return HF_E_INVALID;
@@ -1124,17 +1125,11 @@ int launch_h(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, hipStream_
   const int gx = (walk && nblocks > resident) ? resident : nblocks;
   dim3 grid(gx, co_tiles);
   if (grid.y > 65535) return HF_E_INVALID;
-  // Block order (see csrc/convh_enc.hip launch_enc): tiles-fastest re-reads every input tile once per cout tile from beyond L2,
-  // cout-tiles-fastest streams the weights once per group of resident input tiles instead - taken when that moves fewer bytes
+  // block order: one shared input, every cout tile a column; the tile count is that of ALL tiles, walked or not
   P.swap_xy = 0;
   if (co_tiles > 1 && gx <= 65535) {
     const double in_bytes = (double)P.batch * P.cin * P.h * P.w * 4.0, w_bytes = 9.0 * P.cin * P.cout * 4.0;
-    const double tiles_fast = co_tiles * in_bytes + w_bytes;
-    const double resident_tiles = co_tiles >= 256 ? 1.0 : 256.0 / co_tiles;
-    const double cols_fast = in_bytes + w_bytes * ((double)nblocks / resident_tiles);
-    // (inputs that fit the 256 MB Infinity Cache beside everything else are re-read from there either way: measured neutral at
-    // batch 8 - tools/probes/gen_layers.py, r05j - so only from half of it upward, i.e. in the batched swap's generator calls)
-    if ((g_h_tune & 8) || (in_bytes > 128e6 && cols_fast < 0.5 * tiles_fast)) {
+    if (columns_fastest(in_bytes, in_bytes, w_bytes, co_tiles, nblocks)) {
       P.swap_xy = 1;
       grid = dim3(co_tiles, gx);
     }
@@ -1155,6 +1150,68 @@ int launch_h(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, hipStream_
   return hf_launch_status();
 }
 
+// ---- the tile forms: configuration id (hf_debug_last_path, hf_debug_set_dispatch) -> launch_h -----------------------------
+// Same resolution (register-staged input: the id; pre-split input, DMA-staged: id + 20, forms 51 52 53 55 only):
+//   51: 64 co x 256 px (8 rows), 2 co-waves x 4 pixel-waves, 1x2 MFMA tiles per wave
+//   52: 64 co x 512 px (16 rows), 8 pixel-waves, 2x2 MFMA tiles per wave: 0.67 LDS fragment
+//       reads per MFMA instead of 2 (fewer issue slots beside the MFMAs), needs >= 256 such blocks
+//   53: 32 co x 512 px (16 rows), 8 pixel-waves, 1x2 tiles: layers with cout % 64 != 0 (1024^2: 32)
+//   55/56: 53 with tiles of 128 / 64-pixel rows (4 / 8 rows): longer contiguous row segments for the
+//       HBM-bound 1024^2 layer (+9 % measured)
+//   54: 32 co x 256 px, 4 pixel-waves (256 threads), 80 KB of LDS: TWO resident blocks per CU, so
+//       one block's barrier drains (activation loads, epilogue stores) hide under the other's
+//       MFMAs - the HBM-bound high-resolution layers (few chunks per tile)
+// Transposed (UP; pre-split: id + 20):
+//   61: 64 co x 256 positions x 4 phases, 2 co-waves x 4 pixel-waves, 1x2 MFMA tiles per phase
+//   63: 32 co x 512 positions x 4 phases, 8 pixel-waves (cout % 64 != 0: the 1024^2 layer)
+// One-kernel upsampling StyledConv (FUSE; ids 73 / 93 = register-staged / pre-split input): the shape of 63 -
+//   <1,2,1,8>: 32 co x 512 positions (16 rows x 32), 8 waves x 2 rows, one block per CU - all eight waves in lock-step, so
+//   the VALU-bound epilogue (29 k of a tile's 70 k cycles) and the MFMA loop never overlap.
+//   (Round 4 measured <1,2,1,4> - 8 rows x 32, FOUR waves, TWO independent blocks per CU, 2 x 37.4 KB of stage buffers each
+//   with the FUSE-aware halo size, so that a SIMD issues one block's epilogue under the other block's MFMAs - with both
+//   blocks resident (round 2's "2x slower" was one block per CU: the rim-tile halo size made its LDS 86 KB): bit-identical,
+//   752 vs 602 us on the 1024^2 layer, 546 vs 432, 449 vs 424: every block stages the full weight stage - twice the LDS-DMA
+//   issues per wave - and recomputes 43 % instead of 22 % halo.  Not kept.)
+//   (Round 6, measured and rejected: <1,1,1,16> - the same tile as SIXTEEN waves x one row, four waves per SIMD at 128 registers,
+//   so that the VALU-issue-bound epilogue runs at 2 instead of 3 cycles per instruction (tools/probes/valu_rate.hip): 806 / 519 /
+//   500 us against 670 / 440 / 400 - the A fragment is then read once per 3 instead of 6 MFMAs, the one-phase K loop returns, and
+//   the kernel spills 212 bytes per lane.  profiles/r06g_fuse_16_waves.txt.  The kernel template still instantiates for it.)
+// Only the forms named here are instantiated; an id a mode does not have is HF_E_INVALID.
+template <int CT_TILES_, int PG_, int WAVES_CO_, int WAVES_PX_, int TWMAX_ = 32>
+struct HForm {
+  static constexpr int CT_TILES = CT_TILES_, PG = PG_, WAVES_CO = WAVES_CO_, WAVES_PX = WAVES_PX_, TWMAX = TWMAX_;
+};
+// (hipcc emits the kernels in the order they are first named, and that order is part of the code object: keep the order of
+// the forms below, the operand mode inside the form here and outside it for the one-kernel upsampling conv)
+using HForm63 = HForm<1, 2, 1, 8>;  // also the one-kernel upsampling conv's
+template <bool UP, bool PRE, class F>
+int with_h_form(int cfg, F &&f) {
+  if constexpr (UP) {
+    if (cfg == 63) return f(HForm63{});
+    if (cfg == 61) return f(HForm<1, 2, 2, 4>{});
+  } else {
+    if (cfg == 55) return f(HForm<1, 2, 1, 8, 128>{});
+    if constexpr (!PRE) {
+      if (cfg == 56) return f(HForm<1, 2, 1, 8, 64>{});
+      if (cfg == 54) return f(HForm<1, 2, 1, 4>{});
+    }
+    if (cfg == 53) return f(HForm<1, 2, 1, 8>{});
+    if (cfg == 52) return f(HForm<2, 2, 1, 8>{});
+    if (cfg == 51) return f(HForm<1, 2, 2, 4>{});
+  }
+  return HF_E_INVALID;
+}
+template <int NTERMS, bool UP, bool PRE, bool FUSE, class Form>
+int launch_tile(Form, ConvParams &P, const _Float16 *h, const _Float16 *l, hipStream_t st) {
+  return launch_h<NTERMS, Form::CT_TILES, Form::PG, Form::WAVES_CO, Form::WAVES_PX, UP, Form::TWMAX, PRE, FUSE>(P, h, l, st);
+}
+template <bool UP, bool PRE>
+int launch_form(int cfg, int nterms, ConvParams &P, const _Float16 *h, const _Float16 *l, hipStream_t st) {
+  return with_h_form<UP, PRE>(cfg, [&](auto form) {
+    return with_nterms(nterms, [&](auto nt) { return launch_tile<decltype(nt)::value, UP, PRE, false>(form, P, h, l, st); });
+  });
+}
+
 }  // namespace
 
 namespace hf_detail {
@@ -1170,29 +1227,12 @@ int launch_conv_h(ConvParams &P, int nterms, bool up, const void *wth, const voi
   if (!h || (nterms == 3 && !l)) return HF_E_INVALID;
   int cfg, rc;
   if (up) {
-    // 61: 64 co x 256 positions x 4 phases, 2 co-waves x 4 pixel-waves, 1x2 MFMA tiles per phase
-    // 63: 32 co x 512 positions x 4 phases, 8 pixel-waves (cout % 64 != 0: the 1024^2 layer)
     cfg = (P.cout % 64) ? 63 : 61;
-    if (P.xh) {  // pre-split activations (ids 8x)
-      if (cfg == 63) rc = (nterms == 3) ? launch_h<3, 1, 2, 1, 8, true, 32, true>(P, h, l, st) : launch_h<1, 1, 2, 1, 8, true, 32, true>(P, h, l, st);
-      else rc = (nterms == 3) ? launch_h<3, 1, 2, 2, 4, true, 32, true>(P, h, l, st) : launch_h<1, 1, 2, 2, 4, true, 32, true>(P, h, l, st);
-      if (rc == HF_OK) note_path(5, cfg + 20);
-      return rc;
-    }
-    if (cfg == 63) rc = (nterms == 3) ? launch_h<3, 1, 2, 1, 8, true>(P, h, l, st) : launch_h<1, 1, 2, 1, 8, true>(P, h, l, st);
-    else rc = (nterms == 3) ? launch_h<3, 1, 2, 2, 4, true>(P, h, l, st) : launch_h<1, 1, 2, 2, 4, true>(P, h, l, st);
-    if (rc == HF_OK) note_path(5, cfg);
+    // pre-split activations: ids 8x
+    rc = P.xh ? launch_form<true, true>(cfg, nterms, P, h, l, st) : launch_form<true, false>(cfg, nterms, P, h, l, st);
+    if (rc == HF_OK) note_path(5, P.xh ? cfg + 20 : cfg);
     return rc;
   }
-  // 51: 64 co x 256 px (8 rows), 2 co-waves x 4 pixel-waves, 1x2 MFMA tiles per wave
-  // 52: 64 co x 512 px (16 rows), 8 pixel-waves, 2x2 MFMA tiles per wave: 0.67 LDS fragment
-  //     reads per MFMA instead of 2 (fewer issue slots beside the MFMAs), needs >= 256 such blocks
-  // 53: 32 co x 512 px (16 rows), 8 pixel-waves, 1x2 tiles: layers with cout % 64 != 0 (1024^2: 32)
-  // 55/56: 53 with tiles of 128 / 64-pixel rows (4 / 8 rows): longer contiguous row segments for the
-  //     HBM-bound 1024^2 layer (+9 % measured)
-  // 54: 32 co x 256 px, 4 pixel-waves (256 threads), 80 KB of LDS: TWO resident blocks per CU, so
-  //     one block's barrier drains (activation loads, epilogue stores) hide under the other's
-  //     MFMAs - the HBM-bound high-resolution layers (few chunks per tile)
   cfg = g_force_h;
   if (cfg == 0) {
     // (a tile FORM: same K order as 51, equal bits - tests/test_sim_kernels.py - so it follows the real launch in every mode)
@@ -1211,20 +1251,11 @@ int launch_conv_h(ConvParams &P, int nterms, bool up, const void *wth, const voi
       }
     }
     if (P.rgb_skip) return HF_E_INVALID;  // the finished ToRGB exists in the row pipeline only
-    if (cfg == 55) rc = (nterms == 3) ? launch_h<3, 1, 2, 1, 8, false, 128, true>(P, h, l, st) : launch_h<1, 1, 2, 1, 8, false, 128, true>(P, h, l, st);
-    else if (cfg == 53) rc = (nterms == 3) ? launch_h<3, 1, 2, 1, 8, false, 32, true>(P, h, l, st) : launch_h<1, 1, 2, 1, 8, false, 32, true>(P, h, l, st);
-    else if (cfg == 52) rc = (nterms == 3) ? launch_h<3, 2, 2, 1, 8, false, 32, true>(P, h, l, st) : launch_h<1, 2, 2, 1, 8, false, 32, true>(P, h, l, st);
-    else if (cfg == 51) rc = (nterms == 3) ? launch_h<3, 1, 2, 2, 4, false, 32, true>(P, h, l, st) : launch_h<1, 1, 2, 2, 4, false, 32, true>(P, h, l, st);
-    else return HF_E_INVALID;
+    rc = launch_form<false, true>(cfg, nterms, P, h, l, st);
     if (rc == HF_OK) note_path(5, cfg + 20);
     return rc;
   }
-  if (cfg == 55) rc = (nterms == 3) ? launch_h<3, 1, 2, 1, 8, false, 128>(P, h, l, st) : launch_h<1, 1, 2, 1, 8, false, 128>(P, h, l, st);
-  else if (cfg == 56) rc = (nterms == 3) ? launch_h<3, 1, 2, 1, 8, false, 64>(P, h, l, st) : launch_h<1, 1, 2, 1, 8, false, 64>(P, h, l, st);
-  else if (cfg == 54) rc = (nterms == 3) ? launch_h<3, 1, 2, 1, 4, false>(P, h, l, st) : launch_h<1, 1, 2, 1, 4, false>(P, h, l, st);
-  else if (cfg == 53) rc = (nterms == 3) ? launch_h<3, 1, 2, 1, 8, false>(P, h, l, st) : launch_h<1, 1, 2, 1, 8, false>(P, h, l, st);
-  else if (cfg == 52) rc = (nterms == 3) ? launch_h<3, 2, 2, 1, 8, false>(P, h, l, st) : launch_h<1, 2, 2, 1, 8, false>(P, h, l, st);
-  else rc = (nterms == 3) ? launch_h<3, 1, 2, 2, 4, false>(P, h, l, st) : launch_h<1, 1, 2, 2, 4, false>(P, h, l, st);
+  rc = launch_form<false, false>((cfg >= 52 && cfg <= 56) ? cfg : 51, nterms, P, h, l, st);  // (any other forced id: the 51 shape)
   if (rc == HF_OK) note_path(5, cfg);
   return rc;
 }
@@ -1250,38 +1281,51 @@ extern "C" int hf_conv_split_weights_f16_taps(void *wt_hi, void *wt_lo, const fl
 
 extern "C" unsigned long long hf_f16_overflow_count_convh(int reset) { return hf_f16_overflow_read_tu(reset); }
 
+// What the generator entry points share (as enc_fill for the encoder ones, convh_enc.hip): the checks on operands and shape
+// and the ConvParams fields that follow from them (up: the output plane is the two-pass upsampling conv's
+// intermediate, 2h+1 rows of that pitch, 2w+1 columns valid); gen_tail: noise, bias + leaky ReLU.  An entry point keeps its own.
+static int gen_fill(ConvParams &P, const float *x, const void *x_hi, const void *x_lo, const void *wt_hi, int nterms,
+                    const float *s, const float *d, int batch, int cin, int cout, int h, int w, bool up = false, int tmp_pitch = 0) {
+  if ((!x && !x_hi) || !wt_hi || batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || (nterms != 1 && nterms != 3) ||
+      (nterms == 3 && x_hi && !x_lo) || (up && tmp_pitch < 2 * w + 1))
+    return HF_E_INVALID;
+  P.x = x; P.xh = x_hi; P.xl = x_lo; P.s = s; P.d = d;
+  P.s_bstride = cin; P.d_bstride = cout;
+  P.groups = 1;
+  P.batch = batch; P.cin = cin; P.cout = cout; P.h = h; P.w = w; P.out_h = h; P.out_w = w; P.out_wv = w;
+  if (up) { P.out_h = 2 * h + 1; P.out_w = tmp_pitch; P.out_wv = 2 * w + 1; }
+  P.stride = 1;
+  return HF_OK;
+}
+static int gen_tail(ConvParams &P, const float *noise, const float *noise_w, long long noise_bstride, const float *bias,
+                    float alpha, float scale) {
+  if (noise && !noise_w) return HF_E_INVALID;
+  P.noise = noise; P.noise_w = noise_w; P.bias = bias;
+  P.noise_bstride = noise_bstride;
+  P.act = bias ? ACT_LRELU : ACT_NONE;
+  P.alpha = alpha; P.scale = scale;
+  return HF_OK;
+}
+
 extern "C" int hf_modconv3x3_f16_f32(float *out, const float *x, const void *wt_hi, const void *wt_lo, int nterms,
                                      const float *s, const float *d, const float *noise, const float *noise_w,
                                      long long noise_bstride, const float *bias, int batch, int cin, int cout, int h,
                                      int w, float alpha, float scale, void *stream) {
-  if (!out || !x || !wt_hi || batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || (noise && !noise_w) ||
-      (nterms != 1 && nterms != 3))
-    return HF_E_INVALID;
   ConvParams P{};
-  P.out = out; P.x = x; P.s = s; P.d = d; P.noise = noise; P.noise_w = noise_w; P.bias = bias;
-  P.s_bstride = cin; P.d_bstride = cout;
-  P.groups = 1;
-  P.noise_bstride = noise_bstride;
-  P.batch = batch; P.cin = cin; P.cout = cout; P.h = h; P.w = w; P.out_h = h; P.out_w = w; P.out_wv = w;
-  P.stride = 1;
-  P.act = bias ? ACT_LRELU : ACT_NONE;
-  P.alpha = alpha; P.scale = scale;
+  if (!out || !x || gen_fill(P, x, nullptr, nullptr, wt_hi, nterms, s, d, batch, cin, cout, h, w) != HF_OK ||
+      gen_tail(P, noise, noise_w, noise_bstride, bias, alpha, scale) != HF_OK)
+    return HF_E_INVALID;
+  P.out = out;
   return launch_conv_h(P, nterms, false, wt_hi, wt_lo, (hipStream_t)stream);
 }
 
 extern "C" int hf_modconv3x3_up_f16_f32(float *tmp, const float *x, const void *wt_hi, const void *wt_lo, int nterms,
                                         const float *s, const float *d, int batch, int cin, int cout, int h, int w,
                                         int tmp_pitch, void *stream) {
-  if (!tmp || !x || !wt_hi || batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || tmp_pitch < 2 * w + 1 ||
-      (nterms != 1 && nterms != 3))
-    return HF_E_INVALID;
   ConvParams P{};
-  P.out = tmp; P.x = x; P.s = s; P.d = d;
-  P.s_bstride = cin; P.d_bstride = cout;
-  P.groups = 1;
-  P.batch = batch; P.cin = cin; P.cout = cout; P.h = h; P.w = w; P.out_h = 2 * h + 1; P.out_w = tmp_pitch;
-  P.out_wv = 2 * w + 1;
-  P.stride = 1;
+  if (!tmp || !x || gen_fill(P, x, nullptr, nullptr, wt_hi, nterms, s, d, batch, cin, cout, h, w, true, tmp_pitch) != HF_OK)
+    return HF_E_INVALID;
+  P.out = tmp;
   return launch_conv_h(P, nterms, true, wt_hi, wt_lo, (hipStream_t)stream);
 }
 
@@ -1292,47 +1336,25 @@ extern "C" int hf_modconv3x3_up_blur_f16_f32(float *out, void *split_hi, void *s
                                              int cout, int h, int w, float alpha, float scale, void *stream) {
   // wt_lo NULL: plain fp16 operands (nterms 1, BASELINE.json configs[4]) - then x_lo / split_lo are not used either
   const int nterms = wt_lo ? 3 : 1;
-  if ((!out == !split_hi) || (!x && !x_hi) || !wt_hi || !blur_k1d_x || !blur_k1d_y || batch <= 0 || cin <= 0 || cout <= 0 ||
-      h < 2 || w < 2 || (noise && !noise_w) || (nterms == 3 && x_hi && !x_lo) || (!x_hi && !s) || (cout % 32) || (cin % 16) ||
+  ConvParams P{};
+  if (gen_fill(P, x, x_hi, x_lo, wt_hi, nterms, x_hi ? nullptr : s, d, batch, cin, cout, h, w) != HF_OK ||
+      gen_tail(P, noise, noise_w, noise_bstride, bias, alpha, scale) != HF_OK || (!out == !split_hi) || !blur_k1d_x ||
+      !blur_k1d_y || h < 2 || w < 2 || (!x_hi && !s) || (cout % 32) || (cin % 16) ||
       (split_hi && ((nterms == 3 && !split_lo) || (cout & 7))) || !bias || !(alpha >= 0.0f && alpha <= 1.0f) || !(scale > 0.0f))
     return HF_E_INVALID;  // exactly one output form; the epilogue assumes bias + leaky ReLU (0 <= alpha <= 1), scale > 0
-  ConvParams P{};
-  P.out = out; P.x = x; P.xh = x_hi; P.xl = x_lo; P.s = x_hi ? nullptr : s; P.d = d; P.noise = noise; P.noise_w = noise_w;
-  P.bias = bias;
-  P.s_bstride = cin; P.d_bstride = cout;
-  P.groups = 1;
-  P.noise_bstride = noise_bstride;
-  P.batch = batch; P.cin = cin; P.cout = cout; P.h = h; P.w = w;
+  P.out = out;
   P.out_h = 2 * h; P.out_w = 2 * w; P.out_wv = 2 * w;
-  P.stride = 1;
-  P.act = bias ? ACT_LRELU : ACT_NONE;
-  P.alpha = alpha; P.scale = scale;
   P.oh = split_hi; P.ol = nterms == 3 ? split_lo : nullptr; P.s_next = s_next;
   for (int j = 0; j < 4; ++j) {  // upfirdn2d is a true convolution: flipped taps (op/upfirdn2d.py:186)
     P.blur_kx[j] = blur_k1d_x[3 - j];
     P.blur_ky[j] = blur_k1d_y[3 - j];
   }
   const _Float16 *hi = static_cast<const _Float16 *>(wt_hi), *lo = static_cast<const _Float16 *>(wt_lo);
-  // <1,2,1,8>: 32 co x 512 positions (16 rows x 32), 8 waves x 2 rows, one block per CU - all eight waves in lock-step, so
-  // the VALU-bound epilogue (29 k of a tile's 70 k cycles) and the MFMA loop never overlap.
-  // (Round 4 measured <1,2,1,4> - 8 rows x 32, FOUR waves, TWO independent blocks per CU, 2 x 37.4 KB of stage buffers each
-  // with the FUSE-aware halo size, so that a SIMD issues one block's epilogue under the other block's MFMAs - with both
-  // blocks resident (round 2's "2x slower" was one block per CU: the rim-tile halo size made its LDS 86 KB): bit-identical,
-  // 752 vs 602 us on the 1024^2 layer, 546 vs 432, 449 vs 424: every block stages the full weight stage - twice the LDS-DMA
-  // issues per wave - and recomputes 43 % instead of 22 % halo.  Not kept.)
-  int rc;
-  // (Round 6, measured and rejected: <1,1,1,16> - the same tile as SIXTEEN waves x one row, four waves per SIMD at 128 registers,
-  // so that the VALU-issue-bound epilogue runs at 2 instead of 3 cycles per instruction (tools/probes/valu_rate.hip): 806 / 519 /
-  // 500 us against 670 / 440 / 400 - the A fragment is then read once per 3 instead of 6 MFMAs, the one-phase K loop returns, and
-  // the kernel spills 212 bytes per lane.  profiles/r06g_fuse_16_waves.txt.  The kernel template still instantiates for it.)
-  if (nterms == 3)
-    rc = x_hi ? launch_h<3, 1, 2, 1, 8, true, 32, true, true>(P, hi, lo, (hipStream_t)stream)
-              : launch_h<3, 1, 2, 1, 8, true, 32, false, true>(P, hi, lo, (hipStream_t)stream);
-  else
-    rc = x_hi ? launch_h<1, 1, 2, 1, 8, true, 32, true, true>(P, hi, lo, (hipStream_t)stream)
-              : launch_h<1, 1, 2, 1, 8, true, 32, false, true>(P, hi, lo, (hipStream_t)stream);
-  const int form = x_hi ? 93 : 73;
-  if (rc == HF_OK) note_path(5, form);
+  const int rc = with_nterms(nterms, [&](auto nt) {
+    return x_hi ? launch_tile<decltype(nt)::value, true, true, true>(HForm63{}, P, hi, lo, (hipStream_t)stream)
+                : launch_tile<decltype(nt)::value, true, false, true>(HForm63{}, P, hi, lo, (hipStream_t)stream);
+  });
+  if (rc == HF_OK) note_path(5, x_hi ? 93 : 73);
   return rc;
 }
 
@@ -1348,7 +1370,7 @@ extern "C" int hf_debug_set_tuning(int bits) {
 }
 
 extern "C" int hf_modconv3x3_f16_rgb_slabs(int cout) {
-  // the dispatch below gives a layer with a fused ToRGB the 64-channel-per-wave tile shape when cout % 64 == 0 (cfg 52),
+  // the dispatch above gives a layer with a fused ToRGB the 64-channel-per-wave tile shape when cout % 64 == 0 (cfg 52),
   // else the 32-channel one (53 / 55)
   return cout <= 0 || (cout % 32) ? 0 : ((cout % 64) ? cout / 32 : cout / 64);
 }
@@ -1363,18 +1385,11 @@ extern "C" int hf_modconv3x3_f16_rgb_f32(float *out, const float *x, const void 
                                          long long noise_bstride, const float *bias, int batch, int cin, int cout,
                                          int h, int w, float alpha, float scale, float *rgb_raw, const float *rgb_wt,
                                          const float *rgb_s, void *stream) {
-  if (!out || !x || !wt_hi || batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || (noise && !noise_w) ||
-      (nterms != 1 && nterms != 3) || !rgb_raw || !rgb_wt || !rgb_s || (cout % 32))
-    return HF_E_INVALID;
   ConvParams P{};
-  P.out = out; P.x = x; P.s = s; P.d = d; P.noise = noise; P.noise_w = noise_w; P.bias = bias;
-  P.s_bstride = cin; P.d_bstride = cout;
-  P.groups = 1;
-  P.noise_bstride = noise_bstride;
-  P.batch = batch; P.cin = cin; P.cout = cout; P.h = h; P.w = w; P.out_h = h; P.out_w = w; P.out_wv = w;
-  P.stride = 1;
-  P.act = bias ? ACT_LRELU : ACT_NONE;
-  P.alpha = alpha; P.scale = scale;
+  if (!out || !x || gen_fill(P, x, nullptr, nullptr, wt_hi, nterms, s, d, batch, cin, cout, h, w) != HF_OK ||
+      gen_tail(P, noise, noise_w, noise_bstride, bias, alpha, scale) != HF_OK || !rgb_raw || !rgb_wt || !rgb_s || (cout % 32))
+    return HF_E_INVALID;
+  P.out = out;
   P.rgb_out = rgb_raw; P.rgb_w = rgb_wt; P.rgb_s = rgb_s;
   P.rgb_slabs = hf_modconv3x3_f16_rgb_slabs(cout);
   return launch_conv_h(P, nterms, false, wt_hi, wt_lo, (hipStream_t)stream);
@@ -1386,23 +1401,16 @@ extern "C" int hf_modconv3x3_f16_pre_f32(float *out, const void *x_hi, const voi
                                          int cin, int cout, int h, int w, float alpha, float scale, float *rgb_raw,
                                          const float *rgb_wt, const float *rgb_s, void *split_hi, void *split_lo,
                                          const float *s_next, void *stream) {
-  if ((!out && !rgb_raw && !split_hi) || !x_hi || !wt_hi || batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 ||
-      (noise && !noise_w) || (nterms != 1 && nterms != 3) || (nterms == 3 && !x_lo))
-    return HF_E_INVALID;
-  if (rgb_raw && (!rgb_wt || !rgb_s || (cout % 32))) return HF_E_INVALID;
   ConvParams P{};
-  P.out = out; P.xh = x_hi; P.xl = x_lo; P.d = d; P.noise = noise; P.noise_w = noise_w; P.bias = bias;
-  P.s_bstride = cin; P.d_bstride = cout;
-  P.groups = 1;
-  P.noise_bstride = noise_bstride;
-  P.batch = batch; P.cin = cin; P.cout = cout; P.h = h; P.w = w; P.out_h = h; P.out_w = w; P.out_wv = w;
-  P.stride = 1;
-  P.act = bias ? ACT_LRELU : ACT_NONE;
-  P.alpha = alpha; P.scale = scale;
+  if ((!out && !rgb_raw && !split_hi) || !x_hi ||
+      gen_fill(P, nullptr, x_hi, x_lo, wt_hi, nterms, nullptr, d, batch, cin, cout, h, w) != HF_OK ||
+      gen_tail(P, noise, noise_w, noise_bstride, bias, alpha, scale) != HF_OK)
+    return HF_E_INVALID;
+  if ((rgb_raw && (!rgb_wt || !rgb_s || (cout % 32))) || (split_hi && ((cout & 7) || (nterms == 3 && !split_lo)))) return HF_E_INVALID;
+  P.out = out;
   P.rgb_out = rgb_raw; P.rgb_w = rgb_wt; P.rgb_s = rgb_s;
   P.rgb_slabs = hf_modconv3x3_f16_rgb_slabs(cout);
   P.oh = split_hi; P.ol = split_lo; P.s_next = s_next;
-  if (split_hi && ((cout & 7) || (nterms == 3 && !split_lo))) return HF_E_INVALID;
   return launch_conv_h(P, nterms, false, wt_hi, wt_lo, (hipStream_t)stream);
 }
 
@@ -1416,19 +1424,12 @@ extern "C" int hf_modconv3x3_f16_pre_image_f32(float *image, const void *x_hi, c
                                                int cin, int cout, int h, int w, float alpha, float scale, const float *rgb_wt,
                                                const float *rgb_s, const float *rgb_bias, const float *skip,
                                                const float *kernel4x4, void *stream) {
-  if (!image || !x_hi || !wt_hi || !rgb_wt || !rgb_s || !skip || !kernel4x4 || batch <= 0 || cin != 32 || cout != 32 || h <= 0 ||
-      w <= 0 || (h & 1) || (w & 1) || (noise && !noise_w) || (nterms != 1 && nterms != 3) || (nterms == 3 && !x_lo) || !bias)
+  ConvParams P{};
+  if (!image || !x_hi || !rgb_wt || !rgb_s || !skip || !kernel4x4 || cin != 32 || cout != 32 || (h & 1) || (w & 1) || !bias ||
+      gen_fill(P, nullptr, x_hi, x_lo, wt_hi, nterms, nullptr, d, batch, cin, cout, h, w) != HF_OK ||
+      gen_tail(P, noise, noise_w, noise_bstride, bias, alpha, scale) != HF_OK)
     return HF_E_INVALID;
   if (g_force_h || (g_h_tune & 16)) return HF_E_INVALID;  // the tiled form was asked for (tests, A/B)
-  ConvParams P{};
-  P.xh = x_hi; P.xl = x_lo; P.d = d; P.noise = noise; P.noise_w = noise_w; P.bias = bias;
-  P.s_bstride = cin; P.d_bstride = cout;
-  P.groups = 1;
-  P.noise_bstride = noise_bstride;
-  P.batch = batch; P.cin = cin; P.cout = cout; P.h = h; P.w = w; P.out_h = h; P.out_w = w; P.out_wv = w;
-  P.stride = 1;
-  P.act = ACT_LRELU;
-  P.alpha = alpha; P.scale = scale;
   P.rgb_out = image; P.rgb_w = rgb_wt; P.rgb_s = rgb_s;
   P.rgb_slabs = 1;
   P.rgb_skip = skip; P.rgb_bias = rgb_bias; P.rgb_k4 = kernel4x4;
@@ -1438,15 +1439,9 @@ extern "C" int hf_modconv3x3_f16_pre_image_f32(float *image, const void *x_hi, c
 extern "C" int hf_modconv3x3_up_f16_pre_f32(float *tmp, const void *x_hi, const void *x_lo, const void *wt_hi,
                                             const void *wt_lo, int nterms, const float *d, int batch, int cin, int cout,
                                             int h, int w, int tmp_pitch, void *stream) {
-  if (!tmp || !x_hi || !wt_hi || batch <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0 || tmp_pitch < 2 * w + 1 ||
-      (nterms != 1 && nterms != 3) || (nterms == 3 && !x_lo))
-    return HF_E_INVALID;
   ConvParams P{};
-  P.out = tmp; P.xh = x_hi; P.xl = x_lo; P.d = d;
-  P.s_bstride = cin; P.d_bstride = cout;
-  P.groups = 1;
-  P.batch = batch; P.cin = cin; P.cout = cout; P.h = h; P.w = w; P.out_h = 2 * h + 1; P.out_w = tmp_pitch;
-  P.out_wv = 2 * w + 1;
-  P.stride = 1;
+  if (!tmp || !x_hi || gen_fill(P, nullptr, x_hi, x_lo, wt_hi, nterms, nullptr, d, batch, cin, cout, h, w, true, tmp_pitch) != HF_OK)
+    return HF_E_INVALID;
+  P.out = tmp;
   return launch_conv_h(P, nterms, true, wt_hi, wt_lo, (hipStream_t)stream);
 }

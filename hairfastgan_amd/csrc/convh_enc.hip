@@ -75,6 +75,13 @@ constexpr int enc_npix() {
   return a > b ? a : b;
 }
 
+// LDS of conv_enc_h / conv_enc_s2mt_h and what launch_enc allocates: the stages of a 64-channel x PT-pixel tile (StageLayout,
+// conv_common.h), then in_scale [cin], in_shift [cin]
+template <int NTERMS, int PT, int STRIDE>
+struct EncLayout : StageLayout<NTERMS, 64, enc_npix<PT, STRIDE>()> {
+  static size_t lds_bytes(int cin) { return EncLayout::stage_bytes + EncLayout::cin_table_floats(cin) * sizeof(float); }
+};
+
 // PRE: the activations arrive already affine-transformed, split into fp16 (hi, lo) and K-blocked
 // ([image][cin/8][h][w][8 halves], hf_split_activation_f16; ConvParams::xh / xl): the halo tile is
 // fetched by LDS-DMA like the weights - no per-element loads, no conversion (a shared input feeding
@@ -95,15 +102,13 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX) void conv_enc_h(const Con
   constexpr int NT = 64 * NW;
   constexpr int CT = 32 * CT_TILES * WAVES_CO;  // 64
   constexpr int PT = 32 * PG * WAVES_PX;
-  constexpr int NPIX = enc_npix<PT, STRIDE>();
-  constexpr int NPART = (NTERMS == 3) ? 2 : 1;
-  constexpr int W_UNITS = 9 * 2 * CT;
-  constexpr int X_UNITS = 2 * NPIX;
-  constexpr int BUF_UNITS = NPART * (W_UNITS + X_UNITS);
+  using L = EncLayout<NTERMS, PT, STRIDE>;
+  static_assert(CT == 64, "EncLayout: 64 output channels per block");
+  constexpr int NPIX = L::NPIX, NPART = L::NPART, W_UNITS = L::W_UNITS, X_UNITS = L::X_UNITS, BUF_UNITS = L::BUF_UNITS;
   constexpr int N_WPIECE = NPART * W_UNITS / 64;
   constexpr int ND = (N_WPIECE + NW - 1) / NW;
   constexpr int XE = (X_UNITS + NT - 1) / NT;
-  constexpr int OFF_WL = W_UNITS, OFF_XH = NPART * W_UNITS, OFF_XL = NPART * W_UNITS + X_UNITS;
+  constexpr int OFF_WL = L::OFF_WL, OFF_XH = L::OFF_XH, OFF_XL = L::OFF_XL;
   static_assert(XE <= 8, "conversion schedule: one item per tap-step");
 
   HF_DYN_LDS;
@@ -548,14 +553,13 @@ template <int NTERMS, int MT, bool VSPLIT>
 __global__ __launch_bounds__(512) void conv_enc_s2mt_h(const ConvParams P, const _Float16 *__restrict__ wth_all,
                                                        const _Float16 *__restrict__ wtl_all) {
   constexpr int WAVES_PX = 4, NW = 8, NT = 64 * NW, CT = 64, PT = 128;
-  constexpr int NPIX = enc_npix<PT, 2>();
-  constexpr int NPART = (NTERMS == 3) ? 2 : 1;
-  constexpr int W_UNITS = 9 * 2 * CT, X_UNITS = 2 * NPIX;
-  constexpr int BUF_UNITS = NPART * (W_UNITS + X_UNITS);
+  using L = EncLayout<NTERMS, PT, 2>;  // the stride-2 form's tile: launch_enc<NTERMS, 1, 4, 2> sizes the allocation for both
+  static_assert(CT == 64, "EncLayout: 64 output channels per block");
+  constexpr int NPIX = L::NPIX, NPART = L::NPART, W_UNITS = L::W_UNITS, X_UNITS = L::X_UNITS, BUF_UNITS = L::BUF_UNITS;
   constexpr int N_WPIECE = NPART * W_UNITS / 64;
   constexpr int ND = (N_WPIECE + NW - 1) / NW;
   constexpr int XE = (X_UNITS + NT - 1) / NT;
-  constexpr int OFF_WL = W_UNITS, OFF_XH = NPART * W_UNITS, OFF_XL = NPART * W_UNITS + X_UNITS;
+  constexpr int OFF_WL = L::OFF_WL, OFF_XH = L::OFF_XH, OFF_XL = L::OFF_XL;
 
   HF_DYN_LDS;
   half8 *lds = reinterpret_cast<half8 *>(hf_dyn_lds);  // [2][BUF_UNITS]: W of chunk parity b | X of step parity b
@@ -785,16 +789,17 @@ inline int enc_splitk_plan(long long blocks, int nchunks) {
 // force_splits > 0 (batch-invariant plans): the K partition is given - the canonical plan of run_enc - and only its
 // execution is decided here: one block per slab (grid.z, partial slabs + splitk_reduce) when the output grid alone leaves
 // the chip empty, else ConvParams::vsplit (every block walks all slabs; same bits).
-thread_local int g_s2mt_last = 0;  // 4 / 2: the last stride-2 launch took the multi-tile form with that many tiles (hf_debug_last_path 605 / 606)
+// *s2mt (stride 2): 4 / 2 when the launch took the multi-tile form with that many tiles (hf_debug_last_path 605 / 606), else 0
 
 template <int NTERMS, int PG, int WAVES_PX, int STRIDE, int CT_TILES = 1, int WAVES_CO = 2>
 int launch_enc(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, float *workspace, long long workspace_floats,
-               hipStream_t st, bool plan_only = false, int force_splits = 0) {
+               hipStream_t st, bool plan_only = false, int force_splits = 0, int *s2mt = nullptr) {
   constexpr int CT = 32 * CT_TILES * WAVES_CO, NT = 64 * WAVES_CO * WAVES_PX;
   static_assert(CT == 64, "64 output channels per block");
   constexpr int PT = 32 * PG * WAVES_PX;
-  constexpr int NPIX = enc_npix<PT, STRIDE>();
-  constexpr int NPART = (NTERMS == 3) ? 2 : 1;
+  using L = EncLayout<NTERMS, PT, STRIDE>;
+  constexpr int NPIX = L::NPIX;
+  static_assert(STRIDE != 2 || PT == 128, "conv_enc_s2mt_h carves its LDS for the 128-pixel stride-2 tile");
   if (P.cin % KH || P.cout % CT || P.stride != STRIDE) return HF_E_INVALID;
   if ((long long)P.cin * P.h * P.w >= (1LL << 31)) return HF_E_INVALID;
   P.n_geom = 1;
@@ -824,26 +829,18 @@ int launch_enc(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, float *w
   // the form the launch will take
   dim3 grid(geom_blocks(G), P.co_tiles * groups, P.vsplit ? 1 : P.splits);
   if (grid.y > 65535) return HF_E_INVALID;
-  // Block order (blocks are dispatched x-fastest, 256 at a time): tiles-fastest keeps a column's weights in L2 and re-reads every
-  // input tile once per column from beyond L2 (columns x input bytes); columns-fastest keeps ~256 / columns input tiles in L2 and
-  // re-reads the weights once per such group (weights fit the 256 MB Infinity Cache; the input of a batched pass does not).
-  // Taken when it moves fewer bytes from beyond L2 and no counters are keyed by (x, y) (real split-K keeps tiles-fastest).
+  // block order: a column = (group, channel tile); real split-K keeps tiles-fastest (its arrival counters are keyed by (x, y))
   P.swap_xy = 0;
   if ((P.vsplit || P.splits == 1) && grid.x <= 65535 && grid.y > 1) {
     const double col_in = (double)P.batch * P.cin * P.h * P.w * 4.0;   // input bytes one column reads (hi + lo, or fp32)
     const double in_bytes = col_in * (P.x_gstride ? groups : 1);       // all inputs once
     const double w_bytes = 9.0 * P.cin * P.cout * 4.0 * groups;        // all weights once (hi + lo)
-    const double tiles_fast = (double)grid.y * col_in + w_bytes;
-    const double resident = grid.y >= 256 ? 1.0 : 256.0 / grid.y;      // input tiles in flight at a time
-    const double cols_fast = in_bytes + w_bytes * ((double)grid.x / resident);
-    // (an input that fits the 256 MB Infinity Cache beside the rest is re-read from there either way: from half of it upward;
-    // hf_debug_set_tuning bit 3: tests force the order)
-    if ((g_h_tune & 8) || (col_in > 128e6 && cols_fast < 0.5 * tiles_fast)) {
+    if (columns_fastest(col_in, in_bytes, w_bytes, (int)grid.y, (int)grid.x)) {
       P.swap_xy = 1;
       grid = dim3(grid.y, grid.x, grid.z);
     }
   }
-  const size_t lds = (size_t)2 * NPART * (9 * 2 * CT + 2 * NPIX) * 16 + 2 * ((P.cin + 3) & ~3) * sizeof(float);
+  const size_t lds = L::lds_bytes(P.cin);
   if (lds > 160 * 1024) return HF_E_INVALID;
   // (every rejection of the tile form sits above the plan-only return: a query - hf_conv2d_f16_workspace_floats,
   // hf_conv2d_f16_split_output_ok, which plans with P.oh set - walks the same fall-through chain as the launch)
@@ -855,7 +852,7 @@ int launch_enc(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, float *w
     P.partial = workspace;
     P.counters = splitk_counters_for((long long)grid.x * grid.y);
   }
-  g_s2mt_last = 0;
+  if (s2mt) *s2mt = 0;
   if (P.xh) {
     if constexpr (STRIDE == 2) {
       // several pixel tiles per resident weight stage (conv_enc_s2mt_h) when the launch still fills the chip with MT times
@@ -875,14 +872,13 @@ int launch_enc(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, float *w
       if (mt) {
         const int tb = hf_cdiv(tiles, mt);
         dim3 g2 = P.swap_xy ? dim3(cols, tb, 1) : dim3(tb, cols, 1);
-        if (mt == 4) {
-          if (P.vsplit) hipLaunchKernelGGL((conv_enc_s2mt_h<NTERMS, 4, true>), g2, dim3(NT), lds, st, P, wth, wtl);
-          else hipLaunchKernelGGL((conv_enc_s2mt_h<NTERMS, 4, false>), g2, dim3(NT), lds, st, P, wth, wtl);
-        } else {
-          if (P.vsplit) hipLaunchKernelGGL((conv_enc_s2mt_h<NTERMS, 2, true>), g2, dim3(NT), lds, st, P, wth, wtl);
-          else hipLaunchKernelGGL((conv_enc_s2mt_h<NTERMS, 2, false>), g2, dim3(NT), lds, st, P, wth, wtl);
-        }
-        g_s2mt_last = mt;
+        with_bool(mt == 4, [&](auto four) {
+          with_bool(P.vsplit != 0, [&](auto vs) {
+            hipLaunchKernelGGL((conv_enc_s2mt_h<NTERMS, decltype(four)::value ? 4 : 2, decltype(vs)::value>), g2, dim3(NT), lds, st, P,
+                               wth, wtl);
+          });
+        });
+        if (s2mt) *s2mt = mt;
         return hf_launch_status();
       }
     }
@@ -900,18 +896,17 @@ int launch_enc(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, float *w
       grid = dim3(resident, 1, 1);
     }
   }
-  if (P.xh) {
-    if (P.vsplit)
-      hipLaunchKernelGGL((conv_enc_h<NTERMS, PG, WAVES_PX, STRIDE, true, CT_TILES, WAVES_CO, true>), grid, dim3(NT), lds, st, P, wth, wtl);
-    else
-      hipLaunchKernelGGL((conv_enc_h<NTERMS, PG, WAVES_PX, STRIDE, true, CT_TILES, WAVES_CO>), grid, dim3(NT), lds, st, P, wth, wtl);
-  } else if (P.vsplit) {
-    if constexpr (CT_TILES == 2) return HF_E_INVALID;  // (never planned: see P.vsplit above)
-    else
-      hipLaunchKernelGGL((conv_enc_h<NTERMS, PG, WAVES_PX, STRIDE, false, CT_TILES, WAVES_CO, true>), grid, dim3(NT), lds, st, P, wth, wtl);
-  } else {
-    hipLaunchKernelGGL((conv_enc_h<NTERMS, PG, WAVES_PX, STRIDE, false, CT_TILES, WAVES_CO>), grid, dim3(NT), lds, st, P, wth, wtl);
-  }
+  const bool launched = with_bool(P.xh != nullptr, [&](auto pre) {
+    return with_bool(P.vsplit != 0, [&](auto vs) {
+      constexpr bool PRE = decltype(pre)::value, VS = decltype(vs)::value;
+      if constexpr (VS && !PRE && CT_TILES == 2) return false;  // (never planned: see P.vsplit above)
+      else {
+        hipLaunchKernelGGL((conv_enc_h<NTERMS, PG, WAVES_PX, STRIDE, PRE, CT_TILES, WAVES_CO, VS>), grid, dim3(NT), lds, st, P, wth, wtl);
+        return true;
+      }
+    });
+  });
+  if (!launched) return HF_E_INVALID;
   int rc = hf_launch_status();
   if (rc == HF_OK && P.splits > 1 && !P.vsplit && !P.counters) rc = launch_splitk_reduce(P, true, st);  // deterministic second pass + epilogue
   return rc;
@@ -928,8 +923,9 @@ int run_enc_forms(ConvParams &P, const _Float16 *hi, const _Float16 *lo, float *
     // Eight waves of 1 x 1 MFMA tiles: two waves per SIMD hide the stage latencies, which is worth more here than the
     // 1 instead of 1.33 LDS fragment reads per MFMA of four 1 x 2 waves (tools/probes/stride2.py: 10-25% faster from
     // 64@256^2 to the 11-group style heads, 30-35% on the register-staged path; same accumulation order, equal bits)
-    rc = launch_enc<NTERMS, 1, 4, 2>(P, hi, lo, ws, wsn, st, plan_only, force_splits);
-    if (rc == HF_OK && !plan_only) note_path(6, g_s2mt_last == 4 ? 5 : g_s2mt_last ? 6 : 2);
+    int mt = 0;
+    rc = launch_enc<NTERMS, 1, 4, 2>(P, hi, lo, ws, wsn, st, plan_only, force_splits, &mt);
+    if (rc == HF_OK && !plan_only) note_path(6, mt == 4 ? 5 : mt ? 6 : 2);
     return rc;
   }
   // 64 co x 512 px (8 waves, 2 x 2 MFMA tiles each) when that fills the chip (batched swaps), else
@@ -1116,7 +1112,7 @@ extern "C" int hf_conv2d_f16_split_output_ok(int batch, int cin, int cout, int h
     return 0;
   if (presplit_input) P.xh = P.xl = &P;  // only tested for NULL while planning
   P.oh = &P;                             // a split output is wanted: forms that cannot write one are skipped like in the launch
-  const int rc = (nterms == 3) ? run_enc<3>(P, nullptr, nullptr, nullptr, 0, nullptr, true) : run_enc<1>(P, nullptr, nullptr, nullptr, 0, nullptr, true);
+  const int rc = with_nterms(nterms, [&](auto nt) { return run_enc<decltype(nt)::value>(P, nullptr, nullptr, nullptr, 0, nullptr, true); });
   return (rc == HF_OK && !(P.splits > 1 && !P.vsplit)) ? 1 : 0;
 }
 
@@ -1132,8 +1128,7 @@ extern "C" int hf_conv2d_f16_f32(float *out, const float *x, const void *x_hi, c
   if (rc != HF_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   const _Float16 *hi = static_cast<const _Float16 *>(wt_hi), *lo = static_cast<const _Float16 *>(wt_lo);
-  return (nterms == 3) ? run_enc<3>(P, hi, lo, workspace, workspace_floats, st, false)
-                       : run_enc<1>(P, hi, lo, workspace, workspace_floats, st, false);
+  return with_nterms(nterms, [&](auto nt) { return run_enc<decltype(nt)::value>(P, hi, lo, workspace, workspace_floats, st, false); });
 }
 
 // hf_conv2d_f16_f32 whose result ALSO (or only: out NULL) leaves as the pre-split input of the next fp16-core conv:
@@ -1154,7 +1149,7 @@ extern "C" int hf_conv2d_f16_split_f32(float *out, void *out_hi, void *out_lo, c
   if ((long long)batch * (cout >> 3) * P.out_h * P.out_w >= (1LL << 40)) return HF_E_INVALID;
   hipStream_t st = (hipStream_t)stream;
   const _Float16 *hi = static_cast<const _Float16 *>(wt_hi), *lo = static_cast<const _Float16 *>(wt_lo);
-  return (nterms == 3) ? run_enc<3>(P, hi, lo, nullptr, 0, st, false) : run_enc<1>(P, hi, lo, nullptr, 0, st, false);
+  return with_nterms(nterms, [&](auto nt) { return run_enc<decltype(nt)::value>(P, hi, lo, nullptr, 0, st, false); });
 }
 
 extern "C" int hf_split_activation_f16(void *out_hi, void *out_lo, const float *x, const float *in_scale, const float *in_shift,

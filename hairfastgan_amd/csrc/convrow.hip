@@ -44,6 +44,10 @@ constexpr int kSkCols = kSW / 2 + 8;          // 40 floats of a (row, channel): 
 constexpr int kSkRow = 3 * kSkCols;           // floats of one skip row (three channels)
 constexpr int kSkGroup = 4 * kSkRow;          // 480 floats = 120 units: two copies of 64 lanes
 constexpr int kSkFloats = 4 * kSkGroup + 16 + 4;
+// LDS of conv_rows_h and what launch_conv_rows allocates: the row ring, the epilogue table, then (finished ToRGB) the skip rows
+constexpr int kRingUnits = kRing * kSlotUnits;  // [kRing][kSlotUnits] 16-byte units
+constexpr int kEpFloats = 5 * 32;               // [32] d', [32] bias', [3][32] rgb weights
+constexpr size_t rows_lds_bytes(bool skip) { return (size_t)kRingUnits * 16 + (kEpFloats + (skip ? kSkFloats : 0)) * sizeof(float); }
 
 // NTERMS 3: f16x3 operands (hi, lo); 1: plain fp16 operands (BASELINE.json configs[4]) - no lo weights, no lo row parts, one
 // MFMA per (tap, row) instead of three
@@ -52,8 +56,8 @@ __global__ __launch_bounds__(512, 2) void conv_rows_h(const ConvParams P, const 
                                                       const _Float16 *__restrict__ wtl, int rows_per_block, int segs) {
   HF_DYN_LDS;
   half8 *ring = reinterpret_cast<half8 *>(hf_dyn_lds);                     // [kRing][kSlotUnits]
-  float *ep = reinterpret_cast<float *>(ring + kRing * kSlotUnits);        // [32] d', [32] bias', [3][32] rgb weights
-  float *skr = ep + 5 * 32;                                                 // P.rgb_skip: [4][kSkGroup] skip rows, [16] kernel, [3] bias
+  float *ep = reinterpret_cast<float *>(ring + kRingUnits);                // [kEpFloats]
+  float *skr = ep + kEpFloats;                                              // P.rgb_skip: [4][kSkGroup] skip rows, [16] kernel, [3] bias
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
   const int H = P.h, W = P.w;
   const long long plane = (long long)H * W;
@@ -333,13 +337,11 @@ int launch_conv_rows(ConvParams &P, int nterms, const void *wth, const void *wtl
   const int rows_per_block = P.h / segs;
   const long long blocks = (long long)P.batch * strips * segs;
   if (blocks >= (1LL << 31)) return HF_E_INVALID;
-  const size_t lds = (size_t)kRing * kSlotUnits * 16 + 5 * 32 * sizeof(float) + (P.rgb_skip ? kSkFloats * sizeof(float) : 0);
-  if (nterms == 3)
-    hipLaunchKernelGGL(conv_rows_h<3>, dim3((unsigned)blocks), dim3(512), lds, st, P, static_cast<const _Float16 *>(wth),
-                       static_cast<const _Float16 *>(wtl), rows_per_block, segs);
-  else
-    hipLaunchKernelGGL(conv_rows_h<1>, dim3((unsigned)blocks), dim3(512), lds, st, P, static_cast<const _Float16 *>(wth),
-                       static_cast<const _Float16 *>(wtl), rows_per_block, segs);
+  const size_t lds = rows_lds_bytes(P.rgb_skip != nullptr);
+  with_nterms(nterms, [&](auto nt) {
+    hipLaunchKernelGGL(conv_rows_h<decltype(nt)::value>, dim3((unsigned)blocks), dim3(512), lds, st, P,
+                       static_cast<const _Float16 *>(wth), static_cast<const _Float16 *>(wtl), rows_per_block, segs);
+  });
   return hf_launch_status();
 }
 

@@ -32,6 +32,19 @@ constexpr int KS = 32;   // input channels per LDS stage
 // blocks from which a launch fills the chip without a K split (hf_debug_set_tuning bits 24-31 lower it for tests)
 inline int gemm_fill_blocks() { return ((hf_detail::g_h_tune >> 24) & 255) ? ((hf_detail::g_h_tune >> 24) & 255) : 256; }
 
+// LDS of gemm1x1_h and what launch_gemm allocates, in 16-byte units: two stage buffers [W hi][W lo][X hi][X lo] of a
+// (32 * CW channels) x (64 * PG pixels) tile, KS input channels per stage; the lo parts with f16x3 operands only
+template <int NTERMS, int PG, int CW>
+struct GemmLayout {
+  static constexpr int CT = 32 * CW, PT = 64 * PG;
+  static constexpr int NPART = (NTERMS == 3) ? 2 : 1;
+  static constexpr int W_UNITS = (KS / 8) * CT;  // 16-byte units of one weight part per stage: [chunk 2][kg 2][CT co]
+  static constexpr int X_UNITS = (KS / 8) * PT;  // [kblock 4][PT pixels]
+  static constexpr int BUF_UNITS = NPART * (W_UNITS + X_UNITS);
+  static constexpr int OFF_WL = W_UNITS, OFF_XH = NPART * W_UNITS, OFF_XL = NPART * W_UNITS + X_UNITS;
+  static constexpr size_t lds_bytes = (size_t)2 * BUF_UNITS * 16;
+};
+
 // PRE: the activations arrive already transformed, split into fp16 (hi, lo) and K-blocked ([image][cin/8][h*w][8 halves]:
 // hf_split_activation_f16 / hf_split_activation_mod_f16; ConvParams::xh / xl) and are staged by LDS-DMA like the weights -
 // an input shared by many output-channel tiles (the tap-GEMM's 72, the CLIP MLP's 48) is converted once, not once per block.
@@ -43,12 +56,10 @@ inline int gemm_fill_blocks() { return ((hf_detail::g_h_tune >> 24) & 255) ? ((h
 template <int NTERMS, int PG, bool PRE, bool VSPLIT = false, int CW = 2>
 __global__ __launch_bounds__(128 * CW, 2) void gemm1x1_h(const ConvParams P, const _Float16 *__restrict__ wth_all,
                                                  const _Float16 *__restrict__ wtl_all) {
-  constexpr int NW = 2 * CW, NT = 64 * NW, CT = 32 * CW, PT = 64 * PG;
-  constexpr int NPART = (NTERMS == 3) ? 2 : 1;
-  constexpr int W_UNITS = (KS / 8) * CT;        // 16-byte units of one weight part per stage: [chunk 2][kg 2][64 co]
-  constexpr int X_UNITS = (KS / 8) * PT;        // [kblock 4][PT pixels]
-  constexpr int BUF_UNITS = NPART * (W_UNITS + X_UNITS);
-  constexpr int OFF_WL = W_UNITS, OFF_XH = NPART * W_UNITS, OFF_XL = NPART * W_UNITS + X_UNITS;
+  using L = GemmLayout<NTERMS, PG, CW>;
+  constexpr int NW = 2 * CW, NT = 64 * NW, CT = L::CT, PT = L::PT;
+  constexpr int NPART = L::NPART, W_UNITS = L::W_UNITS, X_UNITS = L::X_UNITS, BUF_UNITS = L::BUF_UNITS;
+  constexpr int OFF_WL = L::OFF_WL, OFF_XH = L::OFF_XH, OFF_XL = L::OFF_XL;
   constexpr int XE = X_UNITS / NT;              // staging items per thread and stage (PG, or PG / 2 with eight waves)
   constexpr int N_WPIECE = NPART * W_UNITS / 64;  // 1 KiB DMA pieces per stage (4 or 8; 8 or 16 with 128 channels)
   constexpr int ND = N_WPIECE / NW;             // per wave
@@ -270,7 +281,6 @@ int launch_gemm(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, hipStre
   P.g[0] = g;
   P.n_geom = 1;
   const int nblocks = g.tiles_x * g.tiles_b;
-  constexpr int NPART = (NTERMS == 3) ? 2 : 1;
   // 128-channel blocks (CW = 4) when the launch still fills the chip with them: a tile FORM - the K order of an output element
   // does not change - so it follows the real launch in every mode (tests/test_sim_gemm.py).  PG 4 only (the 256-pixel tile of
   // the large launches: with the 128-pixel tile - the heads' patch GEMM, 4608 -> 512 x 11 groups - it measured SLOWER, 2075 vs
@@ -280,8 +290,7 @@ int launch_gemm(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, hipStre
                     (long long)nblocks * (P.cout / 128) * groups_ >= 2LL * gemm_fill_blocks();  // (from ONE round of CUs: measured mixed - CLIP fc 66-70 -> 71-75 us, proj 101 -> 92-95, r06ab)
   if (wide) P.co_tiles = P.cout / 128;
   g_gemm_wide_last = wide ? 1 : 0;
-  const int ct = wide ? 128 : 64;
-  const size_t lds = (size_t)2 * NPART * ((KS / 8) * ct + (KS / 8) * PT) * 16;
+  const size_t lds = wide ? GemmLayout<NTERMS, PG, 4>::lds_bytes : GemmLayout<NTERMS, PG, 2>::lds_bytes;
   // batch-invariant plans: P.splits is the canonical K partition (gemm_splits at kCanonBatch); a launch whose output grid
   // fills the chip by itself walks the slabs inside its blocks instead of spreading them over grid.z (same bits)
   P.vsplit = (g_batch_invariant && P.splits > 1 && (long long)nblocks * P.co_tiles * max(1, P.groups) >= gemm_fill_blocks()) ? 1 : 0;
@@ -290,31 +299,27 @@ int launch_gemm(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, hipStre
   // split-K of hf_conv1x1_f16_f32 (P.out = the result tensor): the in-kernel second half when a counter buffer is registered;
   // the tap-GEMM of the small-plane convs (P.out = its own slab workspace, combined by small_combine) keeps raw slabs
   P.counters = (P.splits > 1 && !P.vsplit && P.out != P.partial) ? splitk_counters_for((long long)grid.x * grid.y) : nullptr;
-  if (P.xh) {
-    if (P.stride != 1 || P.s || P.t || (NTERMS == 3 && !P.xl) || P.groups > 1 ||
-        (long long)P.batch * P.cin * P.h * P.w * 2 >= (1LL << 32))
-      return HF_E_INVALID;  // 32-bit unit offsets; the affine went into the split
-    if constexpr (PG == 4) {
-      if (wide) {
-        if (P.vsplit) hipLaunchKernelGGL((gemm1x1_h<NTERMS, PG, true, true, 4>), grid, dim3(512), lds, st, P, wth, wtl);
-        else hipLaunchKernelGGL((gemm1x1_h<NTERMS, PG, true, false, 4>), grid, dim3(512), lds, st, P, wth, wtl);
-        return hf_launch_status();
-      }
-    }
-    if (P.vsplit) hipLaunchKernelGGL((gemm1x1_h<NTERMS, PG, true, true>), grid, dim3(256), lds, st, P, wth, wtl);
-    else hipLaunchKernelGGL((gemm1x1_h<NTERMS, PG, true>), grid, dim3(256), lds, st, P, wth, wtl);
-  } else {
-    if constexpr (PG == 4) {
-      if (wide) {
-        if (P.vsplit) hipLaunchKernelGGL((gemm1x1_h<NTERMS, PG, false, true, 4>), grid, dim3(512), lds, st, P, wth, wtl);
-        else hipLaunchKernelGGL((gemm1x1_h<NTERMS, PG, false, false, 4>), grid, dim3(512), lds, st, P, wth, wtl);
-        return hf_launch_status();
-      }
-    }
-    if (P.vsplit) hipLaunchKernelGGL((gemm1x1_h<NTERMS, PG, false, true>), grid, dim3(256), lds, st, P, wth, wtl);
-    else hipLaunchKernelGGL((gemm1x1_h<NTERMS, PG, false>), grid, dim3(256), lds, st, P, wth, wtl);
-  }
+  if (P.xh && (P.stride != 1 || P.s || P.t || (NTERMS == 3 && !P.xl) || P.groups > 1 ||
+               (long long)P.batch * P.cin * P.h * P.w * 2 >= (1LL << 32)))
+    return HF_E_INVALID;  // 32-bit unit offsets; the affine went into the split
+  with_bool(P.xh != nullptr, [&](auto pre) {
+    with_bool(wide, [&](auto wd) {
+      with_bool(P.vsplit != 0, [&](auto vs) {
+        constexpr int CW = decltype(wd)::value ? 4 : 2;
+        if constexpr (CW == 2 || PG == 4)  // (wide: PG 4 only)
+          hipLaunchKernelGGL((gemm1x1_h<NTERMS, PG, decltype(pre)::value, decltype(vs)::value, CW>), grid, dim3(128 * CW), lds, st, P,
+                             wth, wtl);
+      });
+    });
+  });
   return hf_launch_status();
+}
+
+// the 128-pixel (small) or 256-pixel tile, in the operand mode
+int gemm_form(bool small, int nterms, ConvParams &P, const _Float16 *hi, const _Float16 *lo, hipStream_t st) {
+  return with_bool(small, [&](auto sm) {
+    return with_nterms(nterms, [&](auto nt) { return launch_gemm<decltype(nt)::value, decltype(sm)::value ? 2 : 4>(P, hi, lo, st); });
+  });
 }
 
 }  // namespace
@@ -394,9 +399,7 @@ extern "C" int hf_conv1x1_f16_f32(float *out, const float *x, const void *x_hi, 
   }
   const _Float16 *hi = static_cast<const _Float16 *>(wt_hi), *lo = static_cast<const _Float16 *>(wt_lo);
   const bool small = (long long)oplane * batch <= 128 || oplane <= 128;
-  int rc;
-  if (small) rc = (nterms == 3) ? launch_gemm<3, 2>(P, hi, lo, (hipStream_t)stream) : launch_gemm<1, 2>(P, hi, lo, (hipStream_t)stream);
-  else rc = (nterms == 3) ? launch_gemm<3, 4>(P, hi, lo, (hipStream_t)stream) : launch_gemm<1, 4>(P, hi, lo, (hipStream_t)stream);
+  const int rc = gemm_form(small, nterms, P, hi, lo, (hipStream_t)stream);
   if (rc != HF_OK) return rc;
   note_path(7, g_gemm_wide_last ? 6 : (small ? 1 : 2));
   if (P.splits > 1 && !P.vsplit && !P.counters) {
@@ -519,8 +522,7 @@ static int small_gemm(ConvParams &P, const void *w9_hi, const void *w9_lo, int n
     const long long slots = 2LL * gemm_fill_blocks(), tail = n256 % slots;
     small = n256 > slots && tail > 0 && 2 * tail <= slots;
   }
-  if (small) return (nterms == 3) ? launch_gemm<3, 2>(P, hi, lo, st) : launch_gemm<1, 2>(P, hi, lo, st);
-  return (nterms == 3) ? launch_gemm<3, 4>(P, hi, lo, st) : launch_gemm<1, 4>(P, hi, lo, st);
+  return gemm_form(small, nterms, P, hi, lo, st);
 }
 
 extern "C" long long hf_modconv3x3_small_workspace_floats(int batch, int cin, int cout, int h, int w) {

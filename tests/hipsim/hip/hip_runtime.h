@@ -131,5 +131,50 @@ inline ::hipsim::f32x16 hipsim_mfma_h(hipsim_half8 a, hipsim_half8 b, ::hipsim::
 }
 #define __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, x, y, z) hipsim_mfma_h((a), (b), (c))
 
-#define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
-  ::hipsim::launch([=]() { (kernel)(__VA_ARGS__); }, (grid), (block), (shmem))
+// ---- launch-plan recording (HIPSIM_PLAN=FILE, tools/launch_trace.py --plan): a launch is written down, not run --------------
+// One line per launch: the kernel function's offset inside this library (the tool resolves it through `nm -C`, where
+// every instantiation carries its template argument VALUES), grid, block, dynamic LDS bytes, then the arguments -
+// integers and floats by value, pointers as 0 / P, a ConvParams (any struct with its plan fields) by those fields.
+#include <cstdio>
+#include <type_traits>
+namespace hipsim {
+FILE *plan_file();  // null: recording off
+void plan_head(FILE *f, const void *kernel, Dim3 grid, Dim3 block, size_t shmem);
+template <class T>
+auto plan_struct(FILE *f, const T &p, int) -> decltype((void)p.n_geom, (void)p.rgb_slabs, (void)p.chunks_per_split) {
+  fprintf(f, " {splits=%d cps=%d vsplit=%d swap_xy=%d persist=%d lin=%dx%d co_tiles=%d zslab=%lld n_tiles=%d rgb_slabs=%d xs_max=%d",
+          p.splits, p.chunks_per_split, p.vsplit, p.swap_xy, p.persist, p.lin_x, p.lin_y, p.co_tiles, (long long)p.zslab,
+          p.n_tiles, p.rgb_slabs, p.xs_max);
+  fprintf(f, " dims=%d,%d,%d,%d,%d out=%d,%d,%d stride=%d groups=%d act=%d alpha=%.9g scale=%.9g n_geom=%d", p.batch, p.cin,
+          p.cout, p.h, p.w, p.out_h, p.out_w, p.out_wv, p.stride, p.groups, p.act, p.alpha, p.scale, p.n_geom);
+  for (int i = 0; i < p.n_geom && i < 3; ++i)
+    fprintf(f, " g%d=%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d", i, p.g[i].y0, p.g[i].x0, p.g[i].dh, p.g[i].dw, p.g[i].lg_tw, p.g[i].lg_th,
+            p.g[i].lg_nb, p.g[i].tiles_x, p.g[i].tiles_y, p.g[i].tiles_b, p.g[i].first_block);
+  fprintf(f, " partial=%c counters=%c}", p.partial ? 'P' : '0', p.counters ? 'P' : '0');
+}
+template <class T>
+void plan_struct(FILE *f, const T &, long) { fprintf(f, " S%zu", sizeof(T)); }
+template <class T>
+void plan_arg(FILE *f, const T &v) {
+  if constexpr (std::is_null_pointer_v<T>) fputs(" 0", f);
+  else if constexpr (std::is_pointer_v<T>) fprintf(f, " %c", v ? 'P' : '0');
+  else if constexpr (std::is_floating_point_v<T>) fprintf(f, " %.9g", (double)v);
+  else if constexpr (std::is_integral_v<T> || std::is_enum_v<T>) fprintf(f, " %lld", (long long)v);
+  else plan_struct(f, v, 0);
+}
+template <class... A>
+void plan_record(FILE *f, const void *kernel, Dim3 grid, Dim3 block, size_t shmem, const A &...a) {
+  plan_head(f, kernel, grid, block, shmem);
+  (plan_arg(f, a), ...);
+  fputc('\n', f);
+  fflush(f);
+}
+}  // namespace hipsim
+
+#define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...)                                                  \
+  do {                                                                                                               \
+    if (FILE *hipsim_pf = ::hipsim::plan_file())                                                                     \
+      ::hipsim::plan_record(hipsim_pf, reinterpret_cast<const void *>(+(kernel)), (grid), (block), (shmem), ##__VA_ARGS__); \
+    else                                                                                                             \
+      ::hipsim::launch([=]() { (kernel)(__VA_ARGS__); }, (grid), (block), (shmem));                                  \
+  } while (0)

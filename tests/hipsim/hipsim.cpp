@@ -1,4 +1,5 @@
 // TEST INFRASTRUCTURE - scheduler of the hipsim CPU interpreter (see hip/hip_runtime.h).
+#include <dlfcn.h>
 #include <setjmp.h>
 #include <ucontext.h>
 
@@ -250,6 +251,22 @@ void glds_masked(bool active, int bytes, const float *gsrc_lane, float *lds_wave
   f.op = OP_GLDS_MASKED; f.gsrc = gsrc_lane; f.ldst = lds_wave_base; f.b = active ? 1.0f : 0.0f; f.imm = bytes;
   f.state = WAIT_WAVE;
   yield_to_sched();
+}
+
+FILE *plan_file() {
+  static FILE *f = [] {
+    const char *path = getenv("HIPSIM_PLAN");
+    return (path && *path) ? fopen(path, "a") : nullptr;
+  }();
+  return f;
+}
+
+void plan_head(FILE *f, const void *kernel, Dim3 grid, Dim3 block, size_t shmem) {
+  Dl_info info;
+  const bool ok = dladdr(kernel, &info) != 0 && info.dli_fbase;
+  fprintf(f, "launch @%zx grid=%u,%u,%u block=%u,%u,%u lds=%zu :",
+          ok ? (size_t)(static_cast<const char *>(kernel) - static_cast<const char *>(info.dli_fbase)) : (size_t)0, grid.x, grid.y,
+          grid.z, block.x, block.y, block.z, shmem);
 }
 
 void launch(const std::function<void()> &body, Dim3 grid, Dim3 block, size_t shmem) {
