@@ -90,6 +90,14 @@ constexpr int halo_pixels_max() {
 // UP: the transposed (stride 2) conv of the upsampling StyledConv, as in modconv.hip: 4 output
 // phases (pr,pc) = (ky&1, kx&1) per input position (Y,X) of the (h+1)x(w+1) phase domain, each
 // tap feeding exactly one phase from x[Y - (ky==2), X - (kx==2)]; no zero-insertion flops.
+// Tile families (UP without FUSE): the phase domain is the interior h x w plus the far edge - the row Y = h (corner included)
+// and the column X = w.  With register-staged input (fp32, modulated in staging) the edge is two more tile families of this
+// kernel (launch_h: make_geom(one_image), whole 2-row / 2-column tiles of one image; a block only differs by its addresses).
+// An edge position reads x in three of its nine taps and zero padding in the other six, and such a block costs as much as an
+// interior one: with 512 input channels (one block per tile, one block per CU) the edge blocks were the whole last round of
+// the two 512-channel generator layers - 384 instead of 256 and 576 instead of 512 blocks at batch 8.  With pre-split input
+// (PRE) this kernel is therefore launched over the interior only and conv_up_rim_h (below) writes the edge from its three
+// live taps: equal bits.  hf_debug_set_tuning bit 5 keeps the families here (parity tests, A/B).
 // PRE: the activations arrive pre-split and K-blocked (ConvParams::xh/xl): the stage's halo tile
 // is fetched by LDS-DMA like the weights - no per-element loads, no conversion, no s.
 // FUSE (UP only): the 4x4 blur + noise + bias + leaky ReLU of the upsampling StyledConv (model.py:263,
@@ -1067,6 +1075,145 @@ __global__ __launch_bounds__(256) void split_weights(_Float16 *__restrict__ wth,
   }
 }
 
+// The far edge of the two-pass transposed conv with pre-split input (see "Tile families" above conv_mfma_h): row Y = h
+// (positions X = 0..w, corner included -> output row 2h, columns 0..2w) and column X = w (positions Y = 0..h-1 -> output
+// column 2w, rows 0..2h-1) of the (h+1) x (w+1) phase domain, i.e. exactly what conv_mfma_h's two rim families write.
+// There every tap but three multiplies zero padding: the row is fed by taps 6 7 8 (ky == 2: x[h-1, X], x[h-1, X],
+// x[h-1, X-1]) into phases (0,0) (0,1) (0,0), the column by taps 2 5 8 (kx == 2: x[Y, w-1], x[Y, w-1], x[Y-1, w-1]) into
+// phases (0,0) (1,0) (0,0).  Only those are issued here - same MFMA, same operand roles and lane mapping, chunks ascending,
+// the live taps in tap_at<true> order, the three terms in conv_mfma_h's order; the taps left out only ever added exact zeros
+// to these accumulators: equal bits.
+// One wave (= one block) owns 32 positions x 32 output channels; no LDS: a lane's B fragment is one 16-byte load of its
+// (position, kgroup) unit, its A fragment one 16-byte load of (tap, kgroup, co).  The wave is bound by load latency (9 MFMAs
+// per chunk), so the fragments of RIM_DEPTH chunks are in flight in registers (40 VGPRs per chunk with both parts).
+constexpr int RIM_DEPTH = 3;
+template <int NTERMS>
+__global__ __launch_bounds__(64) void conv_up_rim_h(const ConvParams P, const _Float16 *__restrict__ wth,
+                                                    const _Float16 *__restrict__ wtl, int row_tiles, int pos_tiles) {
+  constexpr int NPART = (NTERMS == 3) ? 2 : 1;
+  const int lane = threadIdx.x & 63;
+  const int li = lane & 31;
+  const int lh = lane >> 5;  // k group of the lane, as in conv_mfma_h
+  // block -> (cout tile, position tile, image), cout tile fastest: neighbouring waves share their activation units
+  const int co_tiles = P.cout / 32;
+  int t = (int)blockIdx.x;
+  const int co0 = (t % co_tiles) * 32;
+  t /= co_tiles;
+  const int pt = t % pos_tiles, b = t / pos_tiles;
+  const bool is_row = pt < row_tiles;
+  const int p = (is_row ? pt : pt - row_tiles) * 32 + li;  // row: X, column: Y
+  const int h = P.h, w = P.w;
+  const int plane = h * w;
+  // the two activation units of the position (inside a channel-block plane): `near` feeds the first two taps, `diag` tap 8;
+  // outside the image (and past the ragged end of the position list) the fragment is zero - loaded from unit 0, then cleared
+  const bool store_ok = is_row ? p <= w : p < h;
+  const bool near_ok = is_row ? p < w : p < h;
+  const bool diag_ok = p >= 1 && (is_row ? p <= w : p < h);
+  const int near_u = near_ok ? (is_row ? (h - 1) * w + p : p * w + (w - 1)) : 0;
+  const int diag_u = diag_ok ? (is_row ? (h - 1) * w + p - 1 : (p - 1) * w + (w - 1)) : 0;
+  const int tap0 = is_row ? 6 : 2, tap1 = is_row ? 7 : 5, tap2 = 8;
+
+  const int nchunks = P.cin / KH;
+  // chunk 0 of the lane: activations [image][cin/8][h][w][8], weights [chunk16][tap][kgroup][cout][8]
+  const long long x_lane = (((long long)b * (P.cin / 8) + lh) * plane) * 16;
+  const long long x_chunk = 2LL * plane * 16;
+  const char *xh = static_cast<const char *>(P.xh) + x_lane;
+  const char *xl = NTERMS == 3 ? static_cast<const char *>(P.xl) + x_lane : nullptr;
+  const long long w_lane = ((long long)lh * P.cout + co0 + li) * 16;
+  const long long w_tap = 2LL * P.cout * 16, w_chunk = 9 * w_tap;
+  const char *wh = reinterpret_cast<const char *>(wth) + w_lane;
+  const char *wl = NTERMS == 3 ? reinterpret_cast<const char *>(wtl) + w_lane : nullptr;
+
+  // the epilogue's table values of the lane's 16 channels, formed as conv_mfma_h forms them (load_s): d * 2^-k
+  const float w_unscale = *reinterpret_cast<const float *>(wth + 9LL * P.cin * P.cout);
+  float dmv[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) dmv[r] = 1.0f;
+  if (P.d) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dmv[r] = P.d[(long long)b * P.d_bstride + co0 + (r & 3) + 8 * (r >> 2) + 4 * lh];
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) dmv[r] *= w_unscale;
+
+  half8 wa[RIM_DEPTH][3][NPART], xa[RIM_DEPTH][2][NPART];  // [slot][tap0 tap1 tap2 | near diag][hi lo]
+  auto load = [&](int slot, int c) {
+    const char *xc[2] = {xh + c * x_chunk, NTERMS == 3 ? xl + c * x_chunk : nullptr};
+    const char *wc[2] = {wh + c * w_chunk, NTERMS == 3 ? wl + c * w_chunk : nullptr};
+#pragma unroll
+    for (int part = 0; part < NPART; ++part) {
+      xa[slot][0][part] = *reinterpret_cast<const half8 *>(xc[part] + (long long)near_u * 16);
+      xa[slot][1][part] = *reinterpret_cast<const half8 *>(xc[part] + (long long)diag_u * 16);
+      wa[slot][0][part] = *reinterpret_cast<const half8 *>(wc[part] + tap0 * w_tap);
+      wa[slot][1][part] = *reinterpret_cast<const half8 *>(wc[part] + tap1 * w_tap);
+      wa[slot][2][part] = *reinterpret_cast<const half8 *>(wc[part] + tap2 * w_tap);
+    }
+  };
+  f32x16 acc0, acc1;  // phase (0,0); phase (0,1) of the row / (1,0) of the column
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = 0.0f;
+  auto mma = [&](f32x16 &acc, const half8 (&a)[NPART], const half8 (&bf)[NPART], bool ok) {
+    // (cleared here, not in load(): a select on the loaded registers there would wait for the load it was just issued behind)
+    const half8 zero = {};
+    half8 bv[NPART];
+#pragma unroll
+    for (int part = 0; part < NPART; ++part) bv[part] = ok ? bf[part] : zero;
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], bv[0], acc, 0, 0, 0);
+    if constexpr (NTERMS == 3) {
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], bv[NPART - 1], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[NPART - 1], bv[0], acc, 0, 0, 0);
+    }
+  };
+
+  // chunk c sits in slot c % RIM_DEPTH; its slot is refilled with chunk c + RIM_DEPTH right after its MFMAs (past the last
+  // chunk the last one is loaded again: no branch around the loads, the round is one basic block)
+  auto chunk = [&](int s) {
+    mma(acc0, wa[s][0], xa[s][0], near_ok);
+    mma(acc1, wa[s][1], xa[s][0], near_ok);
+    mma(acc0, wa[s][2], xa[s][1], diag_ok);
+  };
+#pragma unroll
+  for (int s = 0; s < RIM_DEPTH; ++s) load(s, min(s, nchunks - 1));
+  int c0 = 0;
+  for (; c0 + RIM_DEPTH <= nchunks; c0 += RIM_DEPTH) {  // whole rounds: straight-line, one wait per chunk on its own loads only
+#pragma unroll
+    for (int s = 0; s < RIM_DEPTH; ++s) {
+      chunk(s);
+      load(s, min(c0 + s + RIM_DEPTH, nchunks - 1));
+    }
+  }
+#pragma unroll
+  for (int s = 0; s + 1 < RIM_DEPTH; ++s)  // the last nchunks % RIM_DEPTH chunks are in their slots already
+    if (c0 + s < nchunks) chunk(s);
+
+  // v = acc * (d * 2^-k) into the (2h+1) x pitch intermediate, the values of conv_mfma_h's epilogue: the row's phases (0,0),
+  // (0,1) side by side (the corner X = w has the first only), the column's phases (0,0), (1,0) one below the other
+  if (!store_ok) return;
+  const long long oplane = (long long)P.out_h * P.out_w;
+  float *ob = P.out + ((long long)b * P.cout + co0) * oplane +
+              (is_row ? (long long)(2 * h) * P.out_w + 2 * p : (long long)(2 * p) * P.out_w + 2 * w);
+  const long long second = is_row ? 1 : P.out_w;  // where the second phase goes
+  const bool has_second = !is_row || p < w;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    float *q = ob + (long long)((r & 3) + 8 * (r >> 2) + 4 * lh) * oplane;
+    q[0] = acc0[r] * dmv[r];
+    if (has_second) q[second] = acc1[r] * dmv[r];
+  }
+}
+
+// grid of conv_up_rim_h (launch_h checks it against the 2^31 limit BEFORE its main launch: no half-written intermediate)
+inline long long up_rim_blocks(const ConvParams &P) {
+  return (long long)P.batch * (hf_cdiv(P.w + 1, 32) + hf_cdiv(P.h, 32)) * (P.cout / 32);
+}
+template <int NTERMS>
+int launch_up_rim(const ConvParams &P, const _Float16 *wth, const _Float16 *wtl, hipStream_t st) {
+  const int row_tiles = hf_cdiv(P.w + 1, 32), col_tiles = hf_cdiv(P.h, 32);
+  hipLaunchKernelGGL((conv_up_rim_h<NTERMS>), dim3((unsigned)up_rim_blocks(P)), dim3(64), 0, st, P, wth, wtl, row_tiles,
+                     row_tiles + col_tiles);
+  return hf_launch_status();
+}
+
 template <int NTERMS, int CT_TILES, int PG, int WAVES_CO, int WAVES_PX, bool UP, int TWMAX = 32, bool PRE = false, bool FUSE = false>
 int launch_h(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, hipStream_t st) {
   using S = HShape<NTERMS, CT_TILES, PG, WAVES_CO, WAVES_PX, UP, TWMAX, FUSE>;
@@ -1091,7 +1238,10 @@ int launch_h(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, hipStream_
     P.g[0].tiles_x = hf_cdiv(P.w, 30); P.g[0].tiles_y = hf_cdiv(P.h, TH - 2); P.g[0].tiles_b = P.batch;
   }
   int nblocks = geom_blocks(P.g[0]);
-  if (UP && !FUSE) {  // + the Y = h row (incl. corner) and the X = w column of the (h+1)x(w+1) phase domain
+  // pre-split input: the far edge runs in conv_up_rim_h behind this launch (hf_debug_set_tuning bit 5: as rim families here)
+  const bool rim_kernel = UP && !FUSE && PRE && !(g_h_tune & 32);
+  if (rim_kernel && up_rim_blocks(P) >= (1LL << 31)) return HF_E_INVALID;  // (cin % 16, cout % 32: checked above)
+  if (UP && !FUSE && !rim_kernel) {  // + the Y = h row (incl. corner) and the X = w column of the (h+1)x(w+1) phase domain
     P.n_geom = 3;
     constexpr int RIM = PT >= 512 ? 4 : 2;
     P.g[1] = make_geom(P.h, 0, 1, P.w + 1, P.batch, PT, nblocks, true, RIM);
@@ -1147,7 +1297,11 @@ int launch_h(ConvParams &P, const _Float16 *wth, const _Float16 *wtl, hipStream_
     hipLaunchKernelGGL((conv_mfma_h<NTERMS, CT_TILES, PG, WAVES_CO, WAVES_PX, false, UP, TWMAX, false, false>), grid, dim3(NT), lds,
                        st, P, wth, wtl);
   }
-  return hf_launch_status();
+  const int rc = hf_launch_status();
+  if constexpr (UP && !FUSE && PRE) {
+    if (rc == HF_OK && rim_kernel) return launch_up_rim<NTERMS>(P, wth, wtl, st);
+  }
+  return rc;
 }
 
 // ---- the tile forms: configuration id (hf_debug_last_path, hf_debug_set_dispatch) -> launch_h -----------------------------

@@ -732,7 +732,10 @@ int hf_debug_set_persistent_blocks(int blocks);
  * bit 2 = hf_conv2d_f16_f32 never uses its 512-pixel tile form,
  * bits 8-15 = the minimum number of 512-pixel blocks / 8 for that form (0 = the default, 512), bits 16-23 = the
  * same for the 256-pixel form (default 384), bit 3 = the fp16-core conv kernels launch their grid columns-fastest whenever that is
- * legal (by default only when it moves fewer bytes from beyond L2; results do not depend on the block order), bits 5-7 = ignored
+ * legal (by default only when it moves fewer bytes from beyond L2; results do not depend on the block order), bit 5 = hf_modconv3x3_up_f16_pre_f32
+ * keeps the far edge of the transposed conv (phase-domain row Y = h and column X = w) as rim tile families of its main launch
+ * instead of launching the interior only, followed by the edge kernel conv_up_rim_h (csrc/convh.hip; the edge kernel issues the
+ * three taps that read the image in the main kernel's order, the six left out add exact zeros: equal bits), bits 6-7 = ignored
  * (timing ablations of the row-pipeline kernel, removed), bits 24-31 = the block count from which a launch counts as filling the
  * chip by itself (0 = the default, 256; batch-invariant plans: such a launch runs its K partition inside its blocks instead
  * of spreading it over the grid - tests reach that form on small shapes with it).  Results of the generator
