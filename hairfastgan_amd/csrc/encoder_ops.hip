@@ -54,7 +54,8 @@ __global__ void bn_fold(float *__restrict__ scale, float *__restrict__ shift, co
   shift[i] = beta[i] + ((conv_bias ? conv_bias[i] : 0.0f) - mean[i]) * g;
 }
 
-// one wave per plane (small planes); 16-byte loads when the plane size allows
+// one wave per plane (small planes); 16-byte loads when the plane size and the alignment of x allow (hw % 4 == 0 keeps
+// every plane of an aligned x aligned; a contiguous view with a storage offset takes the scalar loop)
 __global__ __launch_bounds__(256) void plane_mean(float *__restrict__ out, const float *__restrict__ x,
                                                   int planes, int hw) {
   const int lane = threadIdx.x & 63;
@@ -62,7 +63,8 @@ __global__ __launch_bounds__(256) void plane_mean(float *__restrict__ out, const
   if (p >= planes) return;
   const float *src = x + (long long)p * hw;
   float acc = 0.0f;
-  if ((hw & 3) == 0) {
+  const bool vec = (hw & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+  if (vec) {
     const float4 *s4 = reinterpret_cast<const float4 *>(src);
     for (int i = lane; i < (hw >> 2); i += 64) {
       const float4 v = s4[i];
@@ -178,20 +180,28 @@ __global__ __launch_bounds__(256) void adaptive_avgpool(float *__restrict__ out,
 }
 
 // scale_factor 0.5, bilinear, align_corners=False: every output is the centre of a 2x2 cell;
-// same operation order as ATen's upsample_bilinear2d (rows blended, then columns).
+// same operation order as ATen's upsample_bilinear2d (rows blended, then columns).  8-byte loads of the cell's two rows
+// (w is even) where x is 8-byte aligned; four scalar loads into the same expression - the same bits - where it is not.
 __global__ __launch_bounds__(256) void downscale2x(float *__restrict__ out, const float *__restrict__ x, int h,
                                                    int w, long long total) {
   const int oh = h / 2, ow = w / 2;
   const long long stride = (long long)gridDim.x * blockDim.x;
   const int oplane = oh * ow;
+  const bool vec = (reinterpret_cast<uintptr_t>(x) & 7) == 0;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
     const long long pl = i / oplane;
     const int p = (int)(i - pl * oplane);
     const int oy = p / ow, ox = p - oy * ow;
     const float *src = x + pl * (long long)h * w + (long long)(2 * oy) * w + 2 * ox;
-    const float2 a = *reinterpret_cast<const float2 *>(src);
-    const float2 b = *reinterpret_cast<const float2 *>(src + w);
-    out[i] = 0.5f * (0.5f * a.x + 0.5f * a.y) + 0.5f * (0.5f * b.x + 0.5f * b.y);
+    float ax, ay, bx, by;
+    if (vec) {
+      const float2 a = *reinterpret_cast<const float2 *>(src);
+      const float2 b = *reinterpret_cast<const float2 *>(src + w);
+      ax = a.x, ay = a.y, bx = b.x, by = b.y;
+    } else {
+      ax = src[0], ay = src[1], bx = src[w], by = src[w + 1];
+    }
+    out[i] = 0.5f * (0.5f * ax + 0.5f * ay) + 0.5f * (0.5f * bx + 0.5f * by);
   }
 }
 
@@ -593,7 +603,10 @@ extern "C" int hf_bn_fold_f32(float *scale, float *shift, const float *gamma, co
 
 extern "C" int hf_plane_mean_f32(float *out, const float *x, int planes, int hw, void *stream) {
   if (!out || !x || planes <= 0 || hw <= 0) return HF_E_INVALID;
-  if (hw >= 4096 && (hw & 3) == 0 && planes <= 65535 * 32)
+  // the block form issues 16-byte loads of x: its base pointer must be 16-byte aligned too (a contiguous view with a
+  // storage offset takes the wave form, whose scalar loop tolerates it)
+  const bool aligned16 = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+  if (hw >= 4096 && (hw & 3) == 0 && aligned16 && planes <= 65535 * 32)
     hipLaunchKernelGGL(plane_mean_block, dim3(planes), dim3(256), 4 * sizeof(float), (hipStream_t)stream, out, x, hw);
   else
     hipLaunchKernelGGL(plane_mean, dim3(hf_cdiv(planes, 4)), dim3(256), 0, (hipStream_t)stream, out, x, planes, hw);

@@ -6,6 +6,7 @@ inputs are formulas (oracle.synth), nothing is stored but outputs.
 """
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from . import synth
 
@@ -413,3 +414,44 @@ def pipeline_bisenet_params():
     w[[10, 17]] = w[[17, 10]]
     P["conv_out.conv_out.weight"] = w
     return P
+
+
+# ------------------------------------------------------------------------------------
+# morphology (oracle/make_golden.py --only morph -> tests/golden/morph.npz, tests/small_ops_checks.py)
+# ------------------------------------------------------------------------------------
+MORPH_RADII = (0, 1, 3, 5)
+
+
+def morph_masks():
+    """The blob masks of tests/golden/morph.npz: [2, 1, 96, 80] (an ellipse with a hole, a block touching a corner, isolated
+    pixels - one at (0, 0); and the flipped, shifted copy) and [1, 1, 256, 256] (a hair-sized region for radius 30)."""
+    yy, xx = torch.meshgrid(torch.arange(96.0), torch.arange(80.0), indexing="ij")
+    m = (((yy - 44) / 30) ** 2 + ((xx - 38) / 24) ** 2 <= 1.0) & ~(((yy - 40) / 9) ** 2 + ((xx - 36) / 7) ** 2 <= 1.0)
+    m[78:, 62:] = True          # a block touching the bottom right corner (two borders)
+    for y, x in ((0, 0), (3, 70), (90, 5), (12, 12), (60, 77)):
+        m[y, x] = True          # isolated pixels, one of them at (0, 0)
+    m2 = torch.roll(torch.flip(m, (0, 1)), (7, -5), (0, 1))
+    small = torch.stack([m, m2]).float()[:, None]
+    yy, xx = torch.meshgrid(torch.arange(256.0), torch.arange(256.0), indexing="ij")
+    hair = (((yy - 110) / 95) ** 2 + ((xx - 128) / 80) ** 2 <= 1.0) & ~(((yy - 130) / 75) ** 2 + ((xx - 128) / 55) ** 2 <= 1.0)
+    hair[:, :3] |= (yy[:, :3] > 60) & (yy[:, :3] < 90)   # a strand that runs into the left border
+    hair[:2, 100:140] = True                            # and one along the top border
+    return small, hair.float()[None, None]
+
+
+def morph_conditions(mask, dil, ero, radius, erosion_may_be_empty=False):
+    """What makes the fixture able to fail: neither map trivially full or empty, each differs from the square structuring
+    element's result in every plane, and the input touches at least two borders."""
+    m = mask > 0
+    borders = [bool(m[..., 0, :].any()), bool(m[..., -1, :].any()), bool(m[..., :, 0].any()), bool(m[..., :, -1].any())]
+    assert sum(borders) >= 2
+    if radius < 1:
+        return
+    k = 2 * radius + 1
+    sq_d = F.max_pool2d(mask, k, 1, radius)
+    sq_e = 1.0 - F.max_pool2d(F.pad(1.0 - mask, (radius,) * 4, value=1.0), k, 1, 0)  # outside the image counts as unset
+    for name, got, sq in (("dilated", dil, sq_d), ("eroded", ero, sq_e)):
+        frac = float(got.mean())
+        if not (name == "eroded" and erosion_may_be_empty and frac == 0.0):
+            assert 0.02 <= frac <= 0.98, (name, radius, frac)
+            assert bool((got != sq).flatten(1).any(1).all()), (name, radius, "equals the square element")

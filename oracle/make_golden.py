@@ -77,7 +77,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
     ap.add_argument("--skip-big", action="store_true")
     ap.add_argument("--only", default=None,
-                    help="comma list of sections to (re)generate (default all): basic,gen64,gen1024,enc_units,encoders,glue,pp,latent,shape,bisenet,sean")
+                    help="comma list of sections to (re)generate (default all): basic,gen64,gen1024,enc_units,encoders,glue,morph,pp,latent,shape,bisenet,sean")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     torch.set_grad_enabled(False)
@@ -372,6 +372,20 @@ def main():
     d_ref, e_ref = RefDilateErosion(dilate_erosion=5, device="cpu").mask(mask5)
     g["dilate5"], g["erode5"] = np.packbits(d_ref.numpy().astype(np.uint8)), np.packbits(e_ref.numpy().astype(np.uint8))
     np.savez_compressed(os.path.join(args.out, "glue.npz"), **g)
+
+    # ---------------- (vi-a) morphology on blob masks: a fixture that a wrong structuring element or border rule fails ------
+    # (glue.npz's masks are thresholded noise: after three rounds the dilation is full and the erosion empty)
+    if want("morph"):
+        g = {}
+        small, hair = C.morph_masks()
+        for mask, radii, tag in ((small, C.MORPH_RADII, "blob"), (hair, (30,), "hair")):
+            for r in radii:
+                d_ref, e_ref = RefDilateErosion(dilate_erosion=r, device="cpu").mask(mask)
+                C.morph_conditions(mask, d_ref, e_ref, r, erosion_may_be_empty=r == 30)
+                g[f"{tag}_dilate{r}"] = np.packbits(d_ref.numpy().astype(np.uint8))
+                g[f"{tag}_erode{r}"] = np.packbits(e_ref.numpy().astype(np.uint8))
+                print(f"morph {tag} radius {r}: dilated {float(d_ref.mean()):.3f} eroded {float(e_ref.mean()):.3f} set", flush=True)
+        np.savez_compressed(os.path.join(args.out, "morph.npz"), **g)
 
     if not args.skip_big and want("pp"):
         import argparse as _ap

@@ -482,6 +482,11 @@ def test_glue_stencils_vs_reference_golden(golden):
     d, e = DilateErosion(5, dev).mask(mask5)
     assert np.array_equal(np.packbits(d.cpu().numpy().astype(np.uint8)), G["dilate5"])
     assert np.array_equal(np.packbits(e.cpu().numpy().astype(np.uint8)), G["erode5"])
+    # blob masks (tests/golden/morph.npz): neither map full or empty, the diamond told from the square, set pixels on the
+    # borders; and radius 64 against the iterated cross
+    from tests import small_ops_checks as K
+
+    K.check_dilate_erode_morph(lambda m, r: DilateErosion(r, dev).mask(m), dev, golden)
 
 
 def test_per_object_conv_precision():

@@ -112,6 +112,11 @@ def test_glue_stencils_vs_reference_golden(simlib, golden):
     mask = (C.unit_input("glue/mask", (3, 1, 48, 48)) > 0.3).float()
     d, e = M.dilate_erode(simlib, None, mask, 3)
     assert torch.equal(d, torch.from_numpy(G["dilate3"])) and torch.equal(e, torch.from_numpy(G["erode3"]))
+    # blob masks (tests/golden/morph.npz): neither map full or empty, the diamond told from the square, set pixels on the
+    # borders; and radius 64 against the iterated cross
+    from tests import small_ops_checks as K
+
+    K.check_dilate_erode_morph(lambda m, r: M.dilate_erode(simlib, None, m, r), torch.device("cpu"), golden)
 
 
 def test_shape_adaptor_blocks_and_layout(simlib, monkeypatch, golden):
