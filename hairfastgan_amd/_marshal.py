@@ -1413,3 +1413,39 @@ def u8_to_unit(lib, st, img):
     out = torch.empty(img.shape, dtype=torch.float32, device=img.device)
     check(lib, lib.hf_u8_to_unit_f32(_p(out), _p(img), img.numel(), st), "hf_u8_to_unit_f32")
     return out
+
+
+# ---- the PNG bytes of --save_all (csrc/export.h; hairfastgan_amd.image_utils has the public forms) ----
+def image_to_bytes(lib, st, images, lo, hi, round_half, interleaved):
+    """fp32 [B,3,H,W] -> uint8 [B,H,W,3] (interleaved) or [B,3,H,W]: t = (x - lo) / (hi - lo), then trunc(clamp(t, 0, 1) * 255)
+    or, round_half, trunc(clamp(t * 255 + 0.5, 0, 255))."""
+    images = _c(images)
+    if images.ndim != 4 or images.shape[1] != 3 or images.numel() == 0:
+        raise ValueError(f"expected images [B,3,H,W] with B, H, W > 0; got {tuple(images.shape)}")
+    lo, hi = float(lo), float(hi)
+    if not hi > lo:
+        raise ValueError(f"value range needs lo < hi; got ({lo}, {hi})")
+    b, _, h, w = images.shape
+    out = torch.empty((b, h, w, 3) if interleaved else (b, 3, h, w), dtype=torch.uint8, device=images.device)
+    check(lib, lib.hf_image_to_bytes_f32(_p(out), _p(images), b, h, w, lo, hi, int(bool(round_half)), int(bool(interleaved)), st),
+          "hf_image_to_bytes_f32")
+    return out
+
+
+def labels_to_rgb(lib, st, labels, palette, unknown_label=255):
+    """int64 labels (any shape) -> uint8 labels.shape + (3,): palette uint8 [n_colors,3] on the labels' device; a label
+    outside the table is black, `unknown_label` white."""
+    if labels.dtype != torch.int64:
+        raise TypeError(f"expected int64 labels; got {labels.dtype}")
+    if palette.dtype != torch.uint8 or palette.ndim != 2 or palette.shape[1] != 3 or palette.shape[0] == 0:
+        raise ValueError(f"the palette is uint8 [n_colors,3]; got {palette.dtype} {tuple(palette.shape)}")
+    if palette.device != labels.device:
+        raise ValueError(f"palette on {palette.device}, labels on {labels.device}")
+    if labels.numel() == 0:
+        raise ValueError("empty label map")
+    labels = labels if labels.is_contiguous() else labels.contiguous()
+    palette = palette if palette.is_contiguous() else palette.contiguous()
+    out = torch.empty(tuple(labels.shape) + (3,), dtype=torch.uint8, device=labels.device)
+    check(lib, lib.hf_labels_to_rgb_i64(_p(out), _p(labels), labels.numel(), _p(palette), palette.shape[0], int(unknown_label), st),
+          "hf_labels_to_rgb_i64")
+    return out

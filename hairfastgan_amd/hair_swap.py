@@ -500,6 +500,8 @@ class Embedding(nn.Module):  # models/Embedding.py:17-117
                     e["W"], e["F"], e["S"] = latent_W[k].unsqueeze(0), latent_F[k].unsqueeze(0), latent_S[k].unsqueeze(0)
                     e["mask"] = masks[k].unsqueeze(0)
                     e["image_256"], e["image_norm_256"] = im_256[k].unsqueeze(0), im_256_norm[k].unsqueeze(0)
+            if kwargs.get("recorder") is not None:  # --save_all (:103-116)
+                kwargs["recorder"].embedding(names_b, latent_W, latent_S, latent_F)
         return name_to_embed
 
 
@@ -515,7 +517,7 @@ class Alignment(nn.Module):  # models/Alignment.py:15-175
         self.dilate_erosion = DilateErosion(dilate_erosion=opts.smooth, device=opts.device)
 
     @torch.inference_mode()
-    def rotate_images(self, pairs, name_to_embed):
+    def rotate_images(self, pairs, name_to_embed, recorder=None):
         """The `Rotate stage` of shape_module (:58-67) for several (im_name1, im_name2) pairs at once: the
         rotated latents are stacked into ONE generator forward (the reference runs one batch-1 forward
         per pair), and so is the shape adaptor on their parses (:74-77: one call for all pairs).
@@ -530,6 +532,8 @@ class Alignment(nn.Module):  # models/Alignment.py:15-175
         seg_in = Embedding.to_bisenet(((I_rot + 1) / 2).clip(0, 1))
         masks = get_segmentation(self.parsing, seg_in)  # the 1024^2 images are parsed (:65-67), both in one call
         targets = self.stages.shape_adaptor(torch.cat([name_to_embed[a]["mask"] for a, _ in todo], 0), masks)
+        if recorder is not None:  # --save_all (:88-89, 92)
+            recorder.rotation(todo, I_rot, masks)
         return {key: (I_rot[k:k + 1], masks[k:k + 1], targets[k:k + 1]) for k, key in enumerate(todo)}
 
     def _target_mask(self, im_name1, im_name2, name_to_embed, rotated=None):
@@ -549,6 +553,8 @@ class Alignment(nn.Module):  # models/Alignment.py:15-175
         inp_mask1, inp_mask2 = e1["mask"], e2["mask"]
         target_mask = self._target_mask(im_name1, im_name2, name_to_embed, rotated)
         hair_mask_target = (target_mask == 13).to(target_mask.dtype)
+        if kwargs.get("recorder") is not None:  # --save_all (:85-93)
+            kwargs["recorder"].shape([(im_name1, im_name2)], name_to_embed, [target_mask])
         if only_target:
             return {"HM_X": hair_mask_target}
         return (inp_mask1, (inp_mask1 == 13).to(inp_mask1.dtype), inp_mask2, (inp_mask2 == 13).to(inp_mask2.dtype),
@@ -561,6 +567,8 @@ class Alignment(nn.Module):  # models/Alignment.py:15-175
         if not pairs:
             return []
         targets = [self._target_mask(a, b, name_to_embed, rotated) for a, b in pairs]
+        if kwargs.get("recorder") is not None:  # --save_all (:85-93)
+            kwargs["recorder"].shape(pairs, name_to_embed, targets)
         stacked = _cat(targets)
         hair = (stacked == 13).to(stacked.dtype)
         return [{"HM_X": hair[j:j + 1]} for j in range(len(pairs))]
@@ -604,7 +612,8 @@ class Alignment(nn.Module):  # models/Alignment.py:15-175
                 sean += list(self.stages.sean_inpaint(torch.cat([e1["image_256"], e2["image_256"]], dim=0),
                                                       torch.cat([e1["mask"], e2["mask"]], dim=0), target_mask))
         _mark("align: SEAN encode + decodes")
-        enc_F = self.latent_encoder(sean)["F"]                                   # e4e batch 2P + generator 0->3
+        enc = self.latent_encoder(sean)                                          # e4e batch 2P + generator 0->3
+        enc_F = enc["F"]
         dilate, erosion = self.dilate_erosion.mask(masks)                        # [3P, 1, 256, 256] each
         free_mask = torch.stack([dilate[0::3], erosion[1::3], erosion[2::3]], dim=1).reshape(-1, *dilate.shape[1:])
         low = 1 - F.interpolate(free_mask.float(), size=(32, 32), mode="bicubic")  # [3P, 1, 32, 32]
@@ -616,6 +625,9 @@ class Alignment(nn.Module):  # models/Alignment.py:15-175
         latent_F_align = intermediate_align + il[:, 0] * (F_1 - intermediate_align)
         latent_F_align = latent_F_out_new + il[:, 1] * (latent_F_align - latent_F_out_new)
         latent_F_align = F_2 + il[:, 2] * (latent_F_align - F_2)
+        if kwargs.get("recorder") is not None:  # --save_all (:85-93, 161-179)
+            kwargs["recorder"].shape([pairs[w[0]] for w in work], name_to_embed, [w[3] for w in work])
+            kwargs["recorder"].alignment([pairs[w[0]] for w in work], sean, enc["W"], enc_F, latent_F_align, [w[1]["S"] for w in work])
         for j, (k, _e1, _e2, _m) in enumerate(work):
             results[k] = {"latent_F_align": latent_F_align[j:j + 1], "HM_X": hair_target[j:j + 1]}
         return results
@@ -687,7 +699,169 @@ class Blending(nn.Module):  # models/Blending.py:11-82
                                         layer_in=F_final)
         out = ((I_final + 1) / 2).clip(0, 1)
         _mark("blend: generator 5->8")
+        if kwargs.get("recorder") is not None:  # --save_all (:71-78)
+            kwargs["recorder"].blending(keys, torch.cat(S_blend, 0), I_blend, S_final, F_final, I_final)
         return [out[t] for t in range(T)]
+
+
+# ---------------------------------------------------------------------------------------------
+# --save_all: what the stages computed, written after the swap
+# ---------------------------------------------------------------------------------------------
+# tools/bench_save_all.py: a dict that receives the wall seconds of the recorder's phases (device-synchronised; None = off)
+SAVE_ALL_TIMES = None
+
+
+class SaveAllRecorder:
+    """The `--save_all` dumps of the reference (utils/save_utils.py; Embedding.py:103-116, Alignment.py:85-93, 161-179,
+    Blending.py:71-78) as a deferred flush.  During a swap the stage methods hand over REFERENCES to the tensors they
+    computed, already batched over triples - no copy, no synchronisation.  After the final image exists
+
+    * `render` runs the reference's five extra generator forwards per triple as TWO calls for everything recorded (0->8 on
+      every embedded image's W; 4->8 on (S, F) of every embedded image, (W, F) of e4e on both SEAN renderings and
+      (S_1, latent_F_align) of every aligned pair), quantises every image on the device (image_utils.to_bytes: the bytes of
+      `save_gen_image`) and colours every parse (image_utils.labels_to_rgb: `mask_to_rgb(mask, 0)`);
+    * `write` copies bytes and latents to the host and writes the reference's layout under
+      save_all_dir / exp_name: W+/ FS/ Shape/ Align/ Blending/ Final/ with its file names (PIL, np.savez).
+
+    Deviation from the reference, on purpose: Embedding.py:94 rebinds `names` in its loop, so its W+/ and FS/ files pair the
+    last image's names with the first images' tensors; here every image is written under every one of its own names."""
+
+    def __init__(self, root):
+        self.root = Path(root)
+        self.exp = [""]
+        self.embeds, self.rotations, self.aligns = [], {}, []
+        self.images, self.masks, self.latents = {}, {}, {}  # path -> (tensor, row) / tensor [1,1,h,w] / {name: tensor}
+        self._rendered = None
+
+    def begin(self, exp_names):
+        """Names of the directories of the triples of the pass that follows (its keys are (t, name), or name for one)."""
+        self.exp = ["" if e is None else str(e) for e in exp_names]
+
+    def _key(self, key):
+        t, name = key if isinstance(key, tuple) else (0, key)
+        return self.root / self.exp[t], name
+
+    # ---- hand-over (references only) ----
+    def embedding(self, names_b, latent_W, latent_S, latent_F):
+        self.embeds.append(([[self._key(n) for n in names] for names in names_b], latent_W, latent_S, latent_F))
+
+    def rotation(self, pairs, I_rot, masks):
+        for k, (a, b) in enumerate(pairs):
+            self.rotations[(self._key(a), self._key(b))] = (I_rot, k, masks[k:k + 1])
+
+    def shape(self, pairs, name_to_embed, targets):
+        for (a, b), target in zip(pairs, targets):
+            (d, n1), (_, n2) = self._key(a), self._key(b)
+            rot = self.rotations.get((self._key(a), self._key(b)))
+            if rot is not None:
+                self.images[d / "Shape" / f"{n2}_rotate_to_{n1}.png"] = (rot[0], rot[1])
+            self.masks[d / "Shape" / f"mask_{n1}.png"] = name_to_embed[a]["mask"]
+            self.masks[d / "Shape" / f"mask_{n2}.png"] = name_to_embed[b]["mask"]
+            self.masks[d / "Shape" / f"mask_{n2}_rotate_to_{n1}.png"] = rot[2] if rot is not None else name_to_embed[b]["mask"]
+            self.masks[d / "Shape" / f"mask_{n1}_{n2}_target.png"] = target
+
+    def alignment(self, pairs, sean, enc_W, enc_F, latent_F_align, S_1):
+        self.aligns.append(([(self._key(a), self._key(b)) for a, b in pairs], sean, enc_W, enc_F.reshape(-1, *enc_F.shape[2:]),
+                            latent_F_align, _cat(S_1)))
+
+    def blending(self, keys, S_blend, I_blend, S_final, F_final, I_final):
+        for t, key in enumerate(keys):
+            d = self._key(key[0])[0]
+            self.images[d / "Blending" / "blending.png"] = (I_blend, t)
+            self.latents[d / "Blending" / "blending.npz"] = {"S_blend": S_blend[t:t + 1]}
+            self.images[d / "Final" / "final.png"] = (I_final, t)
+            self.latents[d / "Final" / "final.npz"] = {"S_final": S_final[t:t + 1], "F_final": F_final[t:t + 1]}
+
+    # ---- after the final image ----
+    @torch.inference_mode()
+    def render(self, generator):
+        """Steps 1-3: enqueues the two extra generator calls, the quantisation and the colouring; no synchronisation."""
+        from .image_utils import labels_to_rgb, to_bytes
+
+        t0 = self._tick()
+        n_img = sum(e[1].shape[0] for e in self.embeds)
+        if n_img:
+            gen_W, _ = generator([_cat([e[1] for e in self.embeds])], input_is_latent=True, return_latents=False)
+            S = [e[2] for e in self.embeds] + [a[2] for a in self.aligns] + [a[5] for a in self.aligns]
+            F_ = [e[3] for e in self.embeds] + [a[3] for a in self.aligns] + [a[4] for a in self.aligns]
+            gen_FS, _ = generator([_cat(S)], input_is_latent=True, return_latents=False, start_layer=4, end_layer=8, layer_in=_cat(F_))
+            row = 0
+            for names_b, W, S_, F_b in self.embeds:
+                for k, names in enumerate(names_b):
+                    for d, n in names:
+                        self.images[d / "W+" / f"{n}.png"] = (gen_W, row + k)
+                        self.latents[d / "W+" / f"{n}.npz"] = {"latent_W": W[k]}
+                        self.images[d / "FS" / f"{n}.png"] = (gen_FS, row + k)
+                        self.latents[d / "FS" / f"{n}.npz"] = {"latent_S": S_[k], "latent_F": F_b[k]}
+                row += len(names_b)
+            out0 = row + sum(2 * len(a[0]) for a in self.aligns)  # first row of the (S_1, latent_F_align) renderings
+            sean_batch = torch.stack([x for a in self.aligns for x in a[1]]) if self.aligns else None  # [2P,3,256,256]
+            for pairs, _sean, _W, _F, F_align, _S in self.aligns:
+                for j, ((d, n1), (_, n2)) in enumerate(pairs):
+                    self.images[d / "Align" / f"{n1}_{n2}_SEAN.png"] = (sean_batch, row - n_img + 2 * j)
+                    self.images[d / "Align" / f"{n2}_{n1}_SEAN.png"] = (sean_batch, row - n_img + 2 * j + 1)
+                    self.images[d / "Align" / f"{n1}_{n2}_e4e.png"] = (gen_FS, row + 2 * j)
+                    self.images[d / "Align" / f"{n2}_{n1}_e4e.png"] = (gen_FS, row + 2 * j + 1)
+                    self.images[d / "Align" / f"{n1}_{n2}_output.png"] = (gen_FS, out0 + j)
+                    self.latents[d / "Align" / f"{n1}_{n2}_F.npz"] = {"latent_F_align": F_align[j:j + 1]}
+                row += 2 * len(pairs)
+                out0 += len(pairs)
+        t1 = self._tick()
+        # one quantisation per batch tensor (each row is written where it lies), one colouring per size of parse
+        batches = {}
+        for tensor, _row in self.images.values():
+            if id(tensor) not in batches:
+                batches[id(tensor)] = to_bytes(tensor.float(), (-1, 1), "floor", "hwc")
+        images = {p: (batches[id(tensor)], row) for p, (tensor, row) in self.images.items()}
+        by_shape = {}
+        for p, m in self.masks.items():
+            by_shape.setdefault(tuple(m.shape), {}).setdefault(id(m), (m, []))[1].append(p)
+        masks = {}
+        for group in by_shape.values():
+            coloured = labels_to_rgb(_cat([m for m, _ in group.values()]))
+            for k, (_m, paths) in enumerate(group.values()):
+                masks.update({p: (coloured, k) for p in paths})
+        self._rendered = (images, masks)
+        self._tick(t0, t1)
+
+    def write(self):
+        """Steps 4-5: bytes and latents to the host, PNG and npz files (directories made as needed)."""
+        from PIL import Image
+
+        if self._rendered is None:
+            raise RuntimeError("SaveAllRecorder.write before render")
+        t0 = self._tick()
+        host = {}
+
+        def fetch(t):
+            if id(t) not in host:
+                host[id(t)] = t.cpu().numpy()
+            return host[id(t)]
+
+        pictures = {p: fetch(t)[row] for part in self._rendered for p, (t, row) in part.items()}
+        latents = {p: {k: v.cpu().numpy() for k, v in d.items()} for p, d in self.latents.items()}
+        t1 = self._tick()
+        for p, arr in pictures.items():
+            p.parent.mkdir(parents=True, exist_ok=True)
+            Image.fromarray(np.ascontiguousarray(arr)).save(p)
+        for p, d in latents.items():
+            p.parent.mkdir(parents=True, exist_ok=True)
+            np.savez(p, **d)
+        if SAVE_ALL_TIMES is not None:
+            SAVE_ALL_TIMES["copy_s"] = SAVE_ALL_TIMES.get("copy_s", 0.0) + t1 - t0
+            SAVE_ALL_TIMES["encode_s"] = SAVE_ALL_TIMES.get("encode_s", 0.0) + time.time() - t1
+        return sorted(list(pictures) + list(latents))
+
+    @staticmethod
+    def _tick(t0=None, t1=None):
+        if SAVE_ALL_TIMES is None:
+            return 0.0
+        torch.cuda.synchronize()
+        now = time.time()
+        if t0 is not None:
+            SAVE_ALL_TIMES["forwards_s"] = SAVE_ALL_TIMES.get("forwards_s", 0.0) + t1 - t0
+            SAVE_ALL_TIMES["bytes_s"] = SAVE_ALL_TIMES.get("bytes_s", 0.0) + now - t1
+        return now
 
 
 class HairFast:
@@ -760,10 +934,6 @@ class HairFast:
         self.conv_precision = conv_precision  # None: the process-wide mode; else this object's own (set per call)
         self.batch_invariant = batch_invariant  # None: the process-wide setting (default on); True / False: this object's own
         conv_precision_scope(conv_precision)  # validates
-        if getattr(args, "save_all", False):
-            raise NotImplementedError(
-                "--save_all (intermediate images / latents written by the reference's utils/save_utils.py, Embedding.py:94-108, "
-                "Alignment.py:84-93, 159-179, Blending.py:70-78) is not implemented by this backend: nothing would be written")
         root = pretrained_root
         given = dict(rotate_state=rotate_state, blend_state=blend_state, clip_image_embed=clip_image_embed,
                      shape_state=shape_state, sean_state=sean_state, sean_mean_codes=sean_mean_codes, clip_state=clip_state)
@@ -810,7 +980,7 @@ class HairFast:
         pairs = []
         for t in range(T):
             pairs += [(key(t, "face"), key(t, "shape"))] + ([] if same[t] else [(key(t, "face"), key(t, "color"))])
-        rotated = self.align.rotate_images(pairs, name_to_embed)               # every Rotate forward as one batch
+        rotated = self.align.rotate_images(pairs, name_to_embed, recorder=kwargs.get("recorder"))  # every Rotate forward as one batch
         _mark("rotate: RotateModel, generator 0->8, BiSeNet @1024, shape adaptor")
         aligns_shape = self.align.align_images_batch([(key(t, "face"), key(t, "shape")) for t in range(T)], name_to_embed,
                                                      rotated=rotated, **kwargs)
@@ -844,6 +1014,12 @@ class HairFast:
         from `landmarks` (three [68,2] arrays, or a callable image (uint8 HWC array) -> [68,2]; default: this object's
         `landmark_detector`), and the return is (final, face, shape, color) with the aligned images, as in the reference.
 
+        args.save_all (read at every call): the intermediate images, parses and latents of every stage are written under
+        args.save_all_dir / (exp_name or "") in the reference's layout (`SaveAllRecorder`).  The extra generator forwards of
+        the dumps run AFTER the final image exists, so the returned image has the same bits with save_all on or off at the
+        same seed - the reference, which draws their noise in the middle of the swap, does not have this property.  If the
+        swap raises, nothing is written.
+
         Randomness: `seed` (default 3407, utils/seed.py:19) makes a swap reproducible on THIS backend; it does not
         reproduce a seeded run of the reference sample for sample: the per-layer noise of a generator forward is one draw
         here (17 in the reference), the FS encoder's discarded generator forward (trainer.py:295, which only advances the
@@ -863,12 +1039,22 @@ class HairFast:
             t0 = time.time()
         seed_ = 3407 if seed is None else seed
 
+        save_all = bool(getattr(self.args, "save_all", False))  # read per call, like the reference's opts.save_all
+
         def run():  # HAIRFAST_CONV_PRECISION=auto: the whole swap again on the fp32 kernels if the fp16 split clamped
             set_seed(seed_)
-            return self._swap_from_tensors(*images, exp_name=exp_name, **kwargs)
+            if not save_all:
+                return self._swap_from_tensors(*images, exp_name=exp_name, **kwargs), None
+            rec = SaveAllRecorder(self.args.save_all_dir)  # a fresh one per attempt: the files are those of the run returned
+            rec.begin([exp_name])
+            final = self._swap_from_tensors(*images, exp_name=exp_name, **dict(kwargs, recorder=rec))
+            rec.render(self.net.generator)  # after the last draw of the swap proper
+            return final, rec
 
         with conv_precision_scope(self.conv_precision), batch_invariant_scope(self.batch_invariant):
-            final_image = run_guarded(run)
+            final_image, rec = run_guarded(run)
+        if rec is not None:
+            rec.write()
         if benchmark:
             torch.cuda.current_stream().synchronize()
             self._times.append(time.time() - t0)
@@ -907,15 +1093,21 @@ class HairFast:
         set_seed(3407 if seed is None else seed)
         return graphs[key](*images).clone()  # (the key carries the mode the graph was captured in)
 
-    def swap_batch(self, triples, seed=None, align=False, landmarks=None, **kwargs):
+    def swap_batch(self, triples, seed=None, align=False, landmarks=None, exp_names=None, **kwargs):
         """Several swaps as ONE batched pass over the hot path (not in the reference: BASELINE.json configs[3],
         "batched HairFast swap").  triples: sequence of (face, shape, color) with the image forms `swap` takes
         (tensors / arrays).  Returns a list of [3, size, size] images in [0, 1], one per triple, equal to what
         `swap` returns for each triple given the same per-layer noise.  align=True: as in `swap`; `landmarks` is one
         triple of [68,2] arrays per triple of images (or a callable), and every entry of the returned list is
-        (final, face, shape, color)."""
+        (final, face, shape, color).  args.save_all: triple t is written under args.save_all_dir / exp_names[t] (default
+        str(t)) with the file names of a single swap; as in `swap`, the finals do not depend on it."""
         cache = {}
         tensors = [[self._as_tensor(img, cache) for img in triple] for triple in triples]
+        if exp_names is None:
+            exp_names = [str(t) for t in range(len(tensors))]
+        exp_names = list(exp_names)
+        if len(exp_names) != len(tensors):
+            raise ValueError(f"exp_names: one name per triple ({len(tensors)}); got {len(exp_names)}")
         if align:
             if landmarks is not None and not callable(landmarks):
                 landmarks = list(landmarks)
@@ -930,19 +1122,31 @@ class HairFast:
         out = [None] * len(prepared)
         seed_ = 3407 if seed is None else seed
 
+        save_all = bool(getattr(self.args, "save_all", False))
+
         def run():
             set_seed(seed_)
+            rec = SaveAllRecorder(self.args.save_all_dir) if save_all else None
+            kw = dict(kwargs, recorder=rec) if save_all else kwargs
             res = [None] * len(prepared)
             if plain:
-                for t, img in zip(plain, self._swap_batch_from_tensors([prepared[t] for t in plain], **kwargs)):
+                if save_all:
+                    rec.begin([exp_names[t] for t in plain])
+                for t, img in zip(plain, self._swap_batch_from_tensors([prepared[t] for t in plain], **kw)):
                     res[t] = img
             for t, tr in enumerate(prepared):
                 if res[t] is None:
-                    res[t] = self._swap_from_tensors(*tr, **kwargs)
-            return res
+                    if save_all:
+                        rec.begin([exp_names[t]])
+                    res[t] = self._swap_from_tensors(*tr, **kw)
+            if save_all:
+                rec.render(self.net.generator)  # after the last draw of the last swap: two generator calls for all triples
+            return res, rec
 
         with conv_precision_scope(self.conv_precision), batch_invariant_scope(self.batch_invariant):
-            finals = run_guarded(run)
+            finals, rec = run_guarded(run)
+        if rec is not None:
+            rec.write()
         if align:
             return [(final, *tr) for final, tr in zip(finals, prepared)]
         return finals

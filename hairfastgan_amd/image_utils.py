@@ -26,6 +26,11 @@ Deviations from the reference, by design:
 * final and face must have the same H x W; the mask follows that size (the reference hard-codes 1024^2);
 * an empty solve region (fpie fails on it) returns save_image's bytes of `final` unchanged;
 * nothing is written to disk and no external tool runs; `poisson_blend` is a batched form the reference lacks.
+
+Also here: the image side of `--save_all` (utils/save_utils.py:12-30) - `to_bytes` (ToPILImage's / save_image's bytes of
+float images, hf_image_to_bytes_f32), `labels_to_rgb` (`mask_to_rgb(pred, 0)`, hf_labels_to_rgb_i64) and `save_image`
+(main.py:44's torchvision call for one image).  The bytes are made on the device: a quarter of the float image crosses to
+the host.
 """
 from types import SimpleNamespace
 
@@ -39,6 +44,15 @@ from .face_parsing import get_segmentation
 HAIR = 13                # CelebAMask label order (face_parsing.LABEL_REMAP)
 DEFAULT_TBLOCK = 8       # sweeps per launch of the Jacobi chain: measured, profiles/poisson_bench.json
 _PARSING = None          # the default BiSeNet, built once (the reference's singleton, my_parsing_util.py:77-79)
+UNKNOWN_LABEL = 255      # drawn white by labels_to_rgb
+# The colour of each of the 19 CelebAMask-HQ labels in a `--save_all` mask PNG (label -> R, G, B; the values
+# `mask_to_rgb(pred, draw_type=0)` of models/CtrlHair/util/mask_color_util.py draws, pinned by tests/golden/mask_colors.npz).
+LABEL_COLORS = {
+    0: (0, 128, 64), 1: (204, 0, 0), 2: (76, 153, 0), 3: (204, 204, 0), 4: (51, 51, 255), 5: (204, 0, 204), 6: (0, 255, 255),
+    7: (51, 255, 255), 8: (102, 51, 0), 9: (255, 0, 0), 10: (102, 204, 0), 11: (255, 255, 0), 12: (0, 0, 153),
+    HAIR: (0, 0, 204), 14: (255, 51, 153), 15: (0, 204, 204), 16: (0, 51, 0), 17: (255, 153, 51), 18: (0, 204, 0),
+}
+_PALETTES = {}           # device -> the table as a 57-byte uint8 buffer [19,3]
 
 
 def default_parsing(device="cuda"):
@@ -148,3 +162,76 @@ def poisson_image_blending_many(final_images, face_images, dilate_erosion=30, ma
         raise ValueError(f"final and face images must all have one size; got {sorted({tuple(x.shape) for x in finals + faces})}")
     out, mask = poisson_blend(torch.stack(finals), torch.stack(faces), dilate_erosion, maxn, parsing=parsing, tblock=tblock)
     return [(_to_pil(out[i].permute(1, 2, 0)), _to_pil(mask[i, 0, :, :, None].expand(-1, -1, 3))) for i in range(len(finals))]
+
+
+# ---------------------------------------------------------------------------------------------
+# bytes of images and label maps (--save_all; csrc/export.h)
+# ---------------------------------------------------------------------------------------------
+ROUNDINGS = {"floor": 0, "nearest": 1}
+LAYOUTS = {"hwc": 1, "chw": 0}
+
+
+def _images_4d(images, what):
+    if not isinstance(images, torch.Tensor):
+        raise TypeError(f"{what}: expected a torch.Tensor; got {type(images)}")
+    if images.dtype != torch.float32:
+        raise TypeError(f"{what}: expected a float32 tensor; got {images.dtype}")
+    if images.ndim not in (3, 4):
+        raise ValueError(f"{what}: expected [3,H,W] or [B,3,H,W]; got {tuple(images.shape)}")
+    if images.shape[-3] != 3:
+        raise ValueError(f"{what}: expected 3 channels; got {tuple(images.shape)}")
+    return images if images.ndim == 4 else images.unsqueeze(0)
+
+
+def to_bytes(images, value_range=(-1, 1), rounding="floor", layout="hwc"):
+    """Float images fp32 [B,3,H,W] (or [3,H,W]) on the GPU -> uint8 [B,H,W,3] (`layout="hwc"`, what PIL takes) or [B,3,H,W]
+    ("chw"), byte-equal to the torch expressions of the reference:
+      rounding="floor",   value_range=(-1, 1): `save_gen_image` - ToPILImage of ((x + 1) / 2).clamp(0, 1): trunc(t * 255)
+      rounding="nearest", value_range=(0, 1):  `torchvision.utils.save_image` - x.mul(255).add(0.5).clamp(0, 255), truncated
+    value_range=(lo, hi) maps t = (x - lo) / (hi - lo) first.  NaN gives 0."""
+    batched = isinstance(images, torch.Tensor) and images.ndim == 4
+    x = _images_4d(images, "to_bytes")
+    if rounding not in ROUNDINGS:
+        raise ValueError(f"rounding must be one of {tuple(ROUNDINGS)}; got {rounding!r}")
+    if layout not in LAYOUTS:
+        raise ValueError(f"layout must be one of {tuple(LAYOUTS)}; got {layout!r}")
+    lo, hi = value_range
+    if not float(hi) > float(lo):
+        raise ValueError(f"value_range needs lo < hi; got {value_range}")
+    require_gpu(x)
+    out = M.image_to_bytes(lib(), stream(), x, lo, hi, ROUNDINGS[rounding], LAYOUTS[layout])
+    return out if batched else out[0]
+
+
+def label_palette(device):
+    """LABEL_COLORS as the uint8 [19,3] device buffer hf_labels_to_rgb_i64 reads (57 bytes, made once per device)."""
+    device = torch.device(device)
+    if device not in _PALETTES:
+        _PALETTES[device] = torch.tensor([LABEL_COLORS[k] for k in range(len(LABEL_COLORS))], dtype=torch.uint8).to(device)
+    return _PALETTES[device]
+
+
+def labels_to_rgb(labels):
+    """`mask_to_rgb(pred, 0)` (models/CtrlHair/util/mask_color_util.py:15-64) on the GPU: int64 label maps [B,1,H,W] (or
+    [B,H,W] / [H,W]) -> uint8 [B,H,W,3] ([H,W,3]).  Labels 0..18 take LABEL_COLORS, 255 is white, anything else black."""
+    if not isinstance(labels, torch.Tensor):
+        raise TypeError(f"labels_to_rgb: expected a torch.Tensor; got {type(labels)}")
+    if labels.dtype != torch.int64:
+        raise TypeError(f"labels_to_rgb: expected int64 labels; got {labels.dtype}")
+    if labels.ndim == 4:
+        if labels.shape[1] != 1:
+            raise ValueError(f"labels_to_rgb: expected one channel [B,1,H,W]; got {tuple(labels.shape)}")
+        labels = labels[:, 0]
+    elif labels.ndim not in (2, 3):
+        raise ValueError(f"labels_to_rgb: expected [B,1,H,W], [B,H,W] or [H,W]; got {tuple(labels.shape)}")
+    require_gpu(labels)
+    return M.labels_to_rgb(lib(), stream(), labels, label_palette(labels.device), UNKNOWN_LABEL)
+
+
+def save_image(image, path, value_range=(0, 1), rounding="nearest", **pil_kwargs):
+    """`torchvision.utils.save_image(image, path)` for ONE image (main.py:44) without torchvision: fp32 [3,H,W] (or
+    [1,3,H,W]) in [0,1] on the GPU -> `to_bytes(value_range, rounding)` and PIL.  `pil_kwargs` go to `Image.save`."""
+    x = _images_4d(image, "save_image")
+    if x.shape[0] != 1:
+        raise ValueError(f"save_image writes one image; got a batch of {x.shape[0]}")
+    _to_pil(to_bytes(x, value_range, rounding, "hwc")[0]).save(path, **pil_kwargs)

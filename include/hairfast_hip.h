@@ -584,6 +584,22 @@ int hf_align_pad_finish_u8(unsigned char *out, float *pre, const float *img, con
 /* torchvision ToTensor on bytes: out = float(in) / 255 (a correctly rounded division, not a reciprocal multiply) */
 int hf_u8_to_unit_f32(float *out, const unsigned char *in, long long n, void *stream);
 
+/* ---- the PNG bytes of --save_all (utils/save_utils.py:12-30: ToPILImage, mask_to_rgb; csrc/export.h) ----
+ * in: planar fp32 [batch, 3, h, w]; out: u8 [batch, h, w, 3] when `interleaved`, else [batch, 3, h, w].
+ * t = (x - lo) / (hi - lo) ((lo, hi) = (-1, 1): (x + 1) / 2; (0, 1): t = x, nothing computed); then
+ *   round_half == 0 (save_gen_image / ToPILImage):  byte = trunc(clamp(t, 0, 1) * 255)
+ *   round_half != 0 (torchvision save_image):       byte = trunc(clamp(t * 255 + 0.5, 0, 255))
+ * every operation one fp32 rounding in that order (no fused multiply-add).  NaN -> 0, +-inf clamp.  Four pixels per
+ * thread (16-byte loads, a 12-byte store) when w % 4 == 0, `in` is 16-byte and `out` 4-byte aligned; else one pixel per
+ * thread, same bytes.  HF_E_INVALID: a null pointer, a non-positive dimension or hi <= lo. */
+int hf_image_to_bytes_f32(unsigned char *out, const float *in, int batch, int h, int w, float lo, float hi, int round_half,
+                          int interleaved, void *stream);
+/* mask_to_rgb(pred, 0) (models/CtrlHair/util/mask_color_util.py:46-63): labels int64 [n_pixels] -> out u8 [n_pixels, 3];
+ * palette u8 [n_colors, 3] on the device.  0 <= label < n_colors: palette[label]; then label == unknown_label: white;
+ * every other value (negative, past the table, above 2^31): black. */
+int hf_labels_to_rgb_i64(unsigned char *out, const long long *labels, long long n_pixels, const unsigned char *palette,
+                         int n_colors, int unknown_label, void *stream);
+
 /* ---- PostProcessModel's latent branch (models/Encoders.py:13-32, 119-131) ----
  * F.layer_norm over the last `dim` elements of each of `rows` rows (biased variance, eps inside the sqrt):
  * gamma / beta [dim] = elementwise affine (both NULL: LayerNorm(elementwise_affine=False), :19), lrelu != 0
