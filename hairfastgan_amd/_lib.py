@@ -75,6 +75,8 @@ SIGNATURES = {
     "hf_align_pad_blur_f32": [_f, _f, _f, _f, _i, _f, _f, _i, _i, _i, _i, _i, _i, _i, _st],
     "hf_align_pad_finish_u8": [_f, _f, _f, _f, _f, _f, _i, _i, _i, _st],
     "hf_u8_to_unit_f32": [_f, _f, _ll, _st],
+    "hf_paste_quad_u8": [_f, _f, _f, ctypes.POINTER(ctypes.c_double), _i, _i, _i, _i, _i, _i, _i, _i, _st],
+    "hf_multiply_u8": [_f, _f, _f, _ll, _st],
     "hf_image_to_bytes_f32": [_f, _f, _i, _i, _i, _fl, _fl, _i, _i, _st],
     "hf_labels_to_rgb_i64": [_f, _f, _ll, _f, _i, _i, _st],
     "hf_maxpool3x3s2_f32": [_f, _f, _ll, _i, _i, _st],

@@ -1415,6 +1415,33 @@ def u8_to_unit(lib, st, img):
     return out
 
 
+# ---- the aligned result pasted back into the photograph (csrc/paste.h; hairfastgan_amd.face_align.paste_back) ----
+def paste_quad_u8(lib, st, photo, src, mask, coef, roi):
+    """In place on photo u8 [C,H,W]: PIL's transform(QUAD, BILINEAR) of src u8 [C,n,n] and of mask u8 [n,n] onto the region
+    roi = (x0, y0, x1, y1) with the coefficients a0..a7 of face_align.quad_coefficients, composited through the warped
+    mask.  -> photo."""
+    if not photo.is_contiguous():
+        raise ValueError("paste works in place: the photograph must be contiguous")
+    photo, src, mask = _planes(photo), _planes(src), _u8(mask)
+    c, h, w = photo.shape
+    n = src.shape[1]
+    if src.shape != (c, n, n) or mask.shape != (n, n):
+        raise ValueError(f"paste: source [C,n,n] and mask [n,n] for a photograph of {c} planes; got {tuple(src.shape)}, {tuple(mask.shape)}")
+    x0, y0, x1, y1 = (int(v) for v in roi)
+    check(lib, lib.hf_paste_quad_u8(_p(photo), _p(src), _p(mask), _coef8(coef), c, h, w, n, x0, y0, x1, y1, st), "hf_paste_quad_u8")
+    return photo
+
+
+def multiply_u8(lib, st, a, b):
+    """PIL's ImageChops.multiply of two uint8 tensors of one shape: a * b / 255, rounded down."""
+    a, b = _u8(a), _u8(b)
+    if a.shape != b.shape:
+        raise ValueError(f"multiply: {tuple(a.shape)} and {tuple(b.shape)} differ in shape")
+    out = torch.empty_like(a)
+    check(lib, lib.hf_multiply_u8(_p(out), _p(a), _p(b), a.numel(), st), "hf_multiply_u8")
+    return out
+
+
 # ---- the PNG bytes of --save_all (csrc/export.h; hairfastgan_amd.image_utils has the public forms) ----
 def image_to_bytes(lib, st, images, lo, hi, round_half, interleaved):
     """fp32 [B,3,H,W] -> uint8 [B,H,W,3] (interleaved) or [B,3,H,W]: t = (x - lo) / (hi - lo), then trunc(clamp(t, 0, 1) * 255)

@@ -104,13 +104,16 @@ __global__ __launch_bounds__(256) void resize_lanczos_v(uint8_t *__restrict__ ou
   }
 }
 
-// Pillow's quad_transform + bilinear_filter8 at output pixel (x, y) of one h x w plane
-__device__ __forceinline__ uint8_t quad_bilinear_sample(const uint8_t *__restrict__ plane, int h, int w, const QuadCoef &q, int x,
-                                                        int y) {
+// Pillow's quad_transform at output pixel (x, y): the source position in an h x w image; false outside it
+__device__ __forceinline__ bool quad_source(const QuadCoef &q, int h, int w, int x, int y, double &xin, double &yin) {
   const double xs = x + 0.5, ys = y + 0.5;
-  double xin = q.a[0] + q.a[1] * xs + q.a[2] * ys + q.a[3] * xs * ys;
-  double yin = q.a[4] + q.a[5] * xs + q.a[6] * ys + q.a[7] * xs * ys;
-  if (!(xin >= 0.0) || xin >= (double)w || !(yin >= 0.0) || yin >= (double)h) return 0;  // (NaN: outside)
+  xin = q.a[0] + q.a[1] * xs + q.a[2] * ys + q.a[3] * xs * ys;
+  yin = q.a[4] + q.a[5] * xs + q.a[6] * ys + q.a[7] * xs * ys;
+  return !(!(xin >= 0.0) || xin >= (double)w || !(yin >= 0.0) || yin >= (double)h);  // (NaN: outside)
+}
+
+// Pillow's bilinear_filter8 of one h x w plane at a position quad_source accepted
+__device__ __forceinline__ uint8_t bilinear_at(const uint8_t *__restrict__ plane, int h, int w, double xin, double yin) {
   xin -= 0.5;
   yin -= 0.5;
   const int xi = xin >= 0.0 ? (int)xin : (int)floor(xin);
@@ -126,6 +129,13 @@ __device__ __forceinline__ uint8_t quad_bilinear_sample(const uint8_t *__restric
   const double v2 = p10 + (p11 - p10) * dx;
   const double v = v1 + (v2 - v1) * dy;
   return (uint8_t)(int)v;
+}
+
+// the two above: Pillow's transform(QUAD, BILINEAR) at output pixel (x, y) of one h x w plane, 0 outside it
+__device__ __forceinline__ uint8_t quad_bilinear_sample(const uint8_t *__restrict__ plane, int h, int w, const QuadCoef &q, int x,
+                                                        int y) {
+  double xin, yin;
+  return quad_source(q, h, w, x, y, xin, yin) ? bilinear_at(plane, h, w, xin, yin) : 0;
 }
 
 // src [planes][h][w] -> out [planes][oh][ow]

@@ -17,12 +17,14 @@
 //   hf_add_bcast_f32             w0 + delta_i, + latent_avg (psp_encoders.py:199, model_utils.py:9-13)
 //   hf_quantize_u8_f32, hf_poisson_*  Poisson image blending, utils/image_utils.py:58-94 (poisson.h)
 //   hf_resize_lanczos_u8, hf_quad_*, hf_align_pad_*  FFHQ face alignment, utils/shape_predictor.py:145-185 (align.h)
+//   hf_paste_quad_u8, hf_multiply_u8  the aligned result pasted back into the photograph (paste.h)
 //   hf_image_to_bytes_f32, hf_labels_to_rgb_i64  the PNG bytes of --save_all, utils/save_utils.py:12-30 (export.h)
 #include <cstdint>
 
 #include "hf_common.h"
 #include "poisson.h"
 #include "align.h"
+#include "paste.h"
 #include "export.h"
 
 // Floating-point contraction: "on" = a multiply and an add are fused only where they are written in ONE expression (or as

@@ -20,6 +20,11 @@ Per image:
 Images are planar uint8 [3,H,W] on the device throughout.  Steps 2, 5 and 6 reproduce Pillow's bytes exactly (integer
 arithmetic; double with one truncation); step 4 is float32 with double accumulation like numpy 1.x + scipy and can differ
 from them by one level only where the value before `rint` sits on a rounding tie.
+
+The way back - `paste_back`: the result computed from an aligned crop put into the photograph where the crop came from
+(no counterpart in the reference).  `paste_plan` inverts the plan to an affine map crop ->
+photograph; the result is reduced to the face's size in the photograph (hf_resize_lanczos_u8) and ONE launch warps it and
+its feather mask onto the region of interest and composites them (hf_paste_quad_u8; csrc/paste.h) - Pillow's bytes again.
 """
 import functools
 
@@ -310,6 +315,161 @@ def align_face(images, landmarks, output_size=1024, transform_size=4096, enable_
         aligned = align_bytes(lib(), stream(), img, lm, output_size, transform_size, enable_padding, fused)
         out.append(unit_float(aligned) if return_tensors else aligned)
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# paste back: the aligned result onto the photograph it was cropped from (csrc/paste.h)
+# ---------------------------------------------------------------------------------------------
+def paste_plan(plan):
+    """The inverse geometry of an `alignment_plan`: the affine map p = A c + b from crop coordinates c in [0, S]^2
+    (S = output_size) to photograph coordinates, both continuous (pixel i covers [i, i + 1)), in float64: dict with
+      A [2,2], b [2], det      the map (columns of A: the crop's x and y axes in the photograph) and det A
+      n                        the side of the result before the warp: the crop's side in photograph pixels, rounded, at most S
+      roi                      (x0, y0, x1, y1): the box of the mapped crop cut at the photograph, or None if they do not meet
+      quad [4,2]               the ROI's corners (NW, SW, SE, NE) in the n x n result: the `data` of Image.transform(QUAD)."""
+    S = plan["output_size"]
+    Q = plan["quad"]
+    o = Q[0] + 0.5                                     # the transform samples at quad + 0.5 (quad_transform)
+    ex = (Q[3] - Q[0]) / S
+    ey = (Q[1] - Q[0]) / S
+    off = np.zeros(2)
+    if plan["pad"] is not None:
+        off = off - np.asarray(plan["pad"][:2], np.float64)
+    if plan["crop"] is not None:
+        off = off + np.asarray(plan["crop"][:2], np.float64)
+    sc = np.ones(2)
+    if plan["rsize"] is not None:                      # the Lanczos shrink scales each axis by its own ratio
+        sc = np.asarray(plan["size_input"], np.float64) / np.asarray(plan["rsize"], np.float64)
+    A = np.stack([ex * sc, ey * sc], axis=1)
+    b = (o + off) * sc
+    det = A[0, 0] * A[1, 1] - A[0, 1] * A[1, 0]
+    if not np.isfinite(det) or det == 0.0:
+        raise ValueError("degenerate alignment plan: the crop has no area in the photograph")
+    side = np.sqrt(abs(det)) * S
+    n = int(min(max(np.rint(side), 1), S))
+    corners = np.array([[0.0, 0.0], [0.0, S], [S, S], [S, 0.0]])
+    px = A[0, 0] * corners[:, 0] + A[0, 1] * corners[:, 1] + b[0]
+    py = A[1, 0] * corners[:, 0] + A[1, 1] * corners[:, 1] + b[1]
+    w, h = plan["size_input"]
+    x0, y0 = max(int(np.floor(px.min())), 0), max(int(np.floor(py.min())), 0)
+    x1, y1 = min(int(np.ceil(px.max())), w), min(int(np.ceil(py.max())), h)
+    out = {"A": A, "b": b, "det": float(det), "side": float(side), "n": n, "roi": None, "quad": None}
+    if x1 > x0 and y1 > y0:
+        out["roi"] = (x0, y0, x1, y1)
+        box = np.array([[x0, y0], [x0, y1], [x1, y1], [x1, y0]], np.float64)
+        dx, dy = box[:, 0] - b[0], box[:, 1] - b[1]
+        k = n / S
+        out["quad"] = np.stack([(A[1, 1] * dx - A[0, 1] * dy) / det * k, (A[0, 0] * dy - A[1, 0] * dx) / det * k], axis=1)
+    return out
+
+
+def feather_mask(n, feather):
+    """The n x n byte mask that fades the pasted square out towards its edges: a smoothstep over the outer `feather` of the
+    side on each axis (0 at the edge, 255 from `feather` inwards), the two axes multiplied; feather = 0: all 255."""
+    n, feather = int(n), float(feather)
+    if n < 1 or not 0.0 <= feather < np.inf:
+        raise ValueError(f"feather_mask: n >= 1 and a finite feather >= 0; got n = {n}, feather = {feather}")
+    x = np.arange(n) + 0.5
+    d = np.minimum(x, n - x) / n
+    r = np.clip(d / feather, 0.0, 1.0) if feather > 0 else np.ones(n)
+    r = r * r * (3.0 - 2.0 * r)
+    return np.floor(255.0 * np.outer(r, r) + 0.5).astype(np.uint8)
+
+
+@functools.lru_cache(maxsize=4)
+def _device_feather(n, feather, device):
+    return torch.from_numpy(feather_mask(n, feather)).to(device)
+
+
+def mask_bytes(mask, size, device):
+    """A crop-space mask [size, size] (tensor or array; uint8, or float in [0,1]: floor(v * 255 + 0.5), clipped) -> uint8
+    on the device."""
+    mask = mask if isinstance(mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(mask)))
+    if tuple(mask.shape) != (size, size):
+        raise ValueError(f"the paste mask is given in crop space, [{size}, {size}]; got {tuple(mask.shape)}")
+    mask = mask.to(device)
+    if mask.dtype is not torch.uint8:
+        if not mask.is_floating_point():
+            raise ValueError(f"the paste mask is uint8 or float in [0,1]; got {mask.dtype}")
+        mask = mask.double().mul(255).add(0.5).floor().clamp(0, 255).to(torch.uint8)
+    return mask.contiguous()
+
+
+def paste_bytes(L, st, photo, result, lm, mask=None, feather=0.1, output_size=1024, stages=None):
+    """One planar uint8 photograph [3,H,W] and the aligned uint8 result [3,S,S] (S = output_size) of the alignment of that
+    photograph from landmarks lm -> a new uint8 [3,H,W]: the photograph with the result warped back to where the crop came
+    from, through the feather mask times `mask` (uint8 [S,S] or None).  stages: a dict that receives the plan, the inverse
+    plan, the resized result and the mask plane (tests)."""
+    S = int(output_size)
+    if photo.ndim != 3 or tuple(result.shape) != (photo.shape[0], S, S):
+        raise ValueError(f"paste: a photograph [3,H,W] and its aligned result [3,{S},{S}]; got {tuple(photo.shape)}, {tuple(result.shape)}")
+    plan = alignment_plan(lm, photo.shape[2], photo.shape[1], S)
+    inv = paste_plan(plan)
+    n = inv["n"]
+    out = photo.clone()
+    small = resize_lanczos(L, st, result, n, n) if n < S else result
+    plane = _device_feather(n, float(feather), photo.device)
+    if mask is not None:
+        if mask.dtype is not torch.uint8 or tuple(mask.shape) != (S, S):
+            raise ValueError(f"paste: the mask is uint8 [{S}, {S}] here (mask_bytes); got {mask.dtype} {tuple(mask.shape)}")
+        user = resize_lanczos(L, st, mask[None], n, n)[0] if n < S else mask
+        plane = M.multiply_u8(L, st, user, plane)
+    if inv["roi"] is not None:
+        x0, y0, x1, y1 = inv["roi"]
+        M.paste_quad_u8(L, st, out, small, plane, quad_coefficients(inv["quad"], x1 - x0, y1 - y0), inv["roi"])
+    if stages is not None:
+        stages.update(plan=plan, inverse=inv, result=small, mask=plane, out=out)
+    return out
+
+
+def result_bytes(result, device):
+    """The result of a swap in the forms `paste_back` takes -> planar uint8 [3,S,S] on the device: a float tensor [3,S,S] in
+    [0,1] with the bytes image_utils.save_image writes (x * 255 + 0.5, clamped, truncated); a uint8 tensor [3,S,S], HWC
+    array or PIL image (what poisson_image_blending returns) as is."""
+    if isinstance(result, torch.Tensor) and result.is_floating_point():
+        from .image_utils import to_bytes as quantise
+
+        if result.ndim != 3:
+            raise ValueError(f"paste: one result [3,S,S] per photograph; got {tuple(result.shape)}")
+        return quantise(result.to(device).float().contiguous(), (0, 1), "nearest", "chw")
+    if not isinstance(result, torch.Tensor):
+        arr = np.asarray(result)
+        if arr.dtype != np.uint8 or arr.ndim != 3 or arr.shape[2] != 3:
+            raise ValueError(f"paste: an image that is not a tensor is uint8 [S,S,3]; got {arr.dtype} {arr.shape}")
+        result = torch.from_numpy(np.ascontiguousarray(arr.transpose(2, 0, 1)))
+    if result.dtype is not torch.uint8 or result.ndim != 3 or result.shape[0] != 3:
+        raise ValueError(f"paste: a result tensor is float in [0,1] or uint8, [3,S,S]; got {result.dtype} {tuple(result.shape)}")
+    return result.to(device).contiguous()
+
+
+@torch.inference_mode()
+def paste_back(photo, result, landmarks, *, mask=None, feather=0.1, output_size=1024, return_tensors=True, device="cuda"):
+    """The inverse of `align_face` for the result of a swap: `photo` (the image forms `swap` takes) with `result` - the
+    [3, output_size, output_size] image computed from its aligned crop: what `swap` or `poisson_image_blending` returns -
+    put back where the crop was taken, from the same [68,2] `landmarks`.  The photograph is not modified.
+
+    mask: optional crop-space [output_size, output_size] weights (uint8, or float in [0,1]) that multiply the feather -
+    e.g. a hair mask; feather: the share of the crop's side over which the square fades out at its edges.
+    photo / result / landmarks (and mask) may be lists of equal length: one launch per photograph, a list is returned.
+    -> float [3,H,W] in [0,1] on the device (uint8 with return_tensors=False)."""
+    many = isinstance(photo, (list, tuple))
+    photos = list(photo) if many else [photo]
+    results = list(result) if many else [result]
+    landmarks = list(landmarks) if many else [landmarks]
+    masks = (list(mask) if many else [mask]) if mask is not None else [None] * len(photos)
+    if not len(photos) == len(results) == len(landmarks) == len(masks):
+        raise ValueError(f"paste_back: one result, one [68,2] landmark array (and one mask) per photograph; got {len(photos)} "
+                         f"photographs, {len(results)} results, {len(landmarks)} landmark arrays, {len(masks)} masks")
+    S = int(output_size)
+    out = []
+    for img, res, lm, mk in zip(photos, results, landmarks, masks):
+        dev = img.device if isinstance(img, torch.Tensor) and img.is_cuda else torch.device(device)
+        img = to_bytes(img, dev)
+        res = result_bytes(res, dev)
+        mk = mask_bytes(mk, S, dev) if mk is not None else None
+        pasted = paste_bytes(lib(), stream(), img, res, check_landmarks(lm), mk, feather, S)
+        out.append(unit_float(pasted) if return_tensors else pasted)
+    return out if many else out[0]
 
 
 def landmarks_for(images_u8, source):

@@ -991,9 +991,10 @@ class HairFast:
         return self.blend.blend_images_batch(aligns_shape, aligns_color, name_to_embed,
                                              [tuple(key(t, n) for n in ("face", "shape", "color")) for t in range(T)], **kwargs)
 
-    def _align_images(self, images, landmarks):
+    def _align_images(self, images, landmarks, with_inputs=False):
         """hair_swap.py:93-94: `align_face(images)` with the landmarks from `landmarks` (arrays or a callable) or this
-        object's `landmark_detector`; NotImplementedError without either - the detector is dlib's, not part of this backend."""
+        object's `landmark_detector`; NotImplementedError without either - the detector is dlib's, not part of this backend.
+        with_inputs: -> (aligned, the photographs' bytes on the device, their landmarks) - what `paste_back` needs."""
         from . import face_align as FA
 
         source = landmarks if landmarks is not None else self.landmark_detector
@@ -1003,16 +1004,20 @@ class HairFast:
                 "HairFast(..., landmark_detector=callable) - the reference's dlib detector and shape predictor "
                 "(utils/shape_predictor.py:49-77) are a third-party model outside this backend (INTEGRATION.md)")
         images = [FA.to_bytes(im, self.args.device) for im in images]
-        return FA.align_face(images, FA.landmarks_for(images, source))
+        lms = FA.landmarks_for(images, source)
+        aligned = FA.align_face(images, lms)
+        return (aligned, images, lms) if with_inputs else aligned
 
     def swap(self, face_img, shape_img, color_img, benchmark=False, align=False, seed=None, exp_name=None, landmarks=None,
-             **kwargs):
+             paste_back=False, **kwargs):
         """hair_swap.py:63-103.  Images: torch.Tensor [3,H,W] (uint8 or float in [0,1]), `PIL.Image.Image`, numpy HWC
         arrays, or file paths (image files decoded through PIL like the reference's `read_image(..., RGB)`; `.npy` arrays).
 
         align=True: arbitrary photographs - each image is first cropped to its face the FFHQ way (hairfastgan_amd.face_align)
         from `landmarks` (three [68,2] arrays, or a callable image (uint8 HWC array) -> [68,2]; default: this object's
         `landmark_detector`), and the return is (final, face, shape, color) with the aligned images, as in the reference.
+        paste_back=True (with align=True; ValueError without): a fifth element, the face photograph with `final` pasted back
+        where its crop was taken (`HairFast.paste_back` with the defaults), float [3,H,W] in [0,1].
 
         args.save_all (read at every call): the intermediate images, parses and latents of every stage are written under
         args.save_all_dir / (exp_name or "") in the reference's layout (`SaveAllRecorder`).  The extra generator forwards of
@@ -1028,10 +1033,12 @@ class HairFast:
         the discarded forward run; _runtime.reference_rng_walk) at the cost of those launches.  Bit-level comparisons with
         the reference inject the noise explicitly
         (Generator.forward(noise= / randomize_noise=False), SPADEGenerator.noise_source; tests/test_gpu_pipeline.py)."""
+        if paste_back and not align:
+            raise ValueError("paste_back=True pastes into the photograph that align=True cropped: it needs align=True")
         cache = {}
         images = [self._as_tensor(img, cache) for img in (face_img, shape_img, color_img)]
         if align:
-            images = self._align_images(images, landmarks)
+            images, photos, lms = self._align_images(images, landmarks, with_inputs=True)
         images = equal_replacer(images)
         set_seed(3407 if seed is None else seed)  # utils/seed.py:19-31
         if benchmark:  # utils/time.py:15-37
@@ -1060,6 +1067,8 @@ class HairFast:
             self._times.append(time.time() - t0)
             print(f"\n{len(self._times)} experiment ended in {self._times[-1]:.3f}(s)\nmin time: {np.min(self._times):.3f}(s), "
                   f"median time: {np.median(self._times):.3f}(s), std time: {np.std(self._times):.3f}(s)", file=sys.stderr)
+        if paste_back:
+            return (final_image, *images, self._paste(final_image, photos[0], lms[0]))
         if align:
             return (final_image, *images)
         return final_image
@@ -1093,14 +1102,17 @@ class HairFast:
         set_seed(3407 if seed is None else seed)
         return graphs[key](*images).clone()  # (the key carries the mode the graph was captured in)
 
-    def swap_batch(self, triples, seed=None, align=False, landmarks=None, exp_names=None, **kwargs):
+    def swap_batch(self, triples, seed=None, align=False, landmarks=None, exp_names=None, paste_back=False, **kwargs):
         """Several swaps as ONE batched pass over the hot path (not in the reference: BASELINE.json configs[3],
         "batched HairFast swap").  triples: sequence of (face, shape, color) with the image forms `swap` takes
         (tensors / arrays).  Returns a list of [3, size, size] images in [0, 1], one per triple, equal to what
         `swap` returns for each triple given the same per-layer noise.  align=True: as in `swap`; `landmarks` is one
         triple of [68,2] arrays per triple of images (or a callable), and every entry of the returned list is
-        (final, face, shape, color).  args.save_all: triple t is written under args.save_all_dir / exp_names[t] (default
+        (final, face, shape, color) - with paste_back=True (final, face, shape, color, pasted), as in `swap`.
+        args.save_all: triple t is written under args.save_all_dir / exp_names[t] (default
         str(t)) with the file names of a single swap; as in `swap`, the finals do not depend on it."""
+        if paste_back and not align:
+            raise ValueError("paste_back=True pastes into the photograph that align=True cropped: it needs align=True")
         cache = {}
         tensors = [[self._as_tensor(img, cache) for img in triple] for triple in triples]
         if exp_names is None:
@@ -1113,8 +1125,9 @@ class HairFast:
                 landmarks = list(landmarks)
                 if len(landmarks) != len(tensors):
                     raise ValueError(f"landmarks: one triple of [68,2] arrays per triple of images ({len(tensors)}); got {len(landmarks)}")
-            tensors = [self._align_images(tr, landmarks if landmarks is None or callable(landmarks) else landmarks[t])
-                       for t, tr in enumerate(tensors)]
+            inputs = [self._align_images(tr, landmarks if landmarks is None or callable(landmarks) else landmarks[t], with_inputs=True)
+                      for t, tr in enumerate(tensors)]
+            tensors = [aligned for aligned, _, _ in inputs]
         prepared = equal_replacer_many(tensors)
         set_seed(3407 if seed is None else seed)
         # a triple that repeats an image takes the reference's shortcuts (no mixing / no second Rotate): one by one
@@ -1147,9 +1160,33 @@ class HairFast:
             finals, rec = run_guarded(run)
         if rec is not None:
             rec.write()
+        if paste_back:
+            return [(final, *tr, self._paste(final, photos[0], lms[0])) for final, tr, (_, photos, lms) in zip(finals, prepared, inputs)]
         if align:
             return [(final, *tr) for final, tr in zip(finals, prepared)]
         return finals
+
+    def _paste(self, final, photo, lm, mask=None, feather=0.1):
+        from . import face_align as FA
+
+        return FA.paste_back(photo, final, lm, mask=mask, feather=feather, output_size=final.shape[-1], device=self.args.device)
+
+    def paste_back(self, final, face_img, landmarks=None, mask=None, feather=0.1):
+        """The inverse of align=True for one result: `face_img` (the photograph `swap(..., align=True)` was given as the
+        face, in the image forms `swap` takes) with `final` (what `swap` returns, or the PIL result of
+        `poisson_image_blending`) pasted back where its crop was taken -> float [3,H,W] in [0,1].  The landmarks are those
+        of the photograph: `landmarks` (one [68,2] array or a callable image -> [68,2]) or this object's
+        `landmark_detector`; NotImplementedError without either.  mask: crop-space weights [S,S] (e.g. a hair mask) that
+        multiply the feather; feather: the share of the crop's side that fades out (hairfastgan_amd.face_align.paste_back)."""
+        from . import face_align as FA
+
+        source = landmarks if landmarks is not None else self.landmark_detector
+        if source is None:
+            self._align_images([], None)  # raises the NotImplementedError of align=True
+        photo = FA.to_bytes(self._as_tensor(face_img), self.args.device)
+        [lm] = FA.landmarks_for([photo], source if callable(source) else [source])
+        size = final.shape[-1] if isinstance(final, torch.Tensor) else np.asarray(final).shape[0]
+        return FA.paste_back(photo, final, lm, mask=mask, feather=feather, output_size=size, device=self.args.device)
 
     def poisson_image_blending(self, final_image, face_img, dilate_erosion=30, maxn=115):
         """utils/image_utils.py:58-94 with this object's BiSeNet: pastes the non-hair region of `face_img` (the image forms

@@ -584,6 +584,19 @@ int hf_align_pad_finish_u8(unsigned char *out, float *pre, const float *img, con
 /* torchvision ToTensor on bytes: out = float(in) / 255 (a correctly rounded division, not a reciprocal multiply) */
 int hf_u8_to_unit_f32(float *out, const unsigned char *in, long long n, void *stream);
 
+/* ---- the aligned result pasted back into the photograph (hairfastgan_amd.face_align.paste_back; csrc/paste.h) ----
+ * One launch, in place on photo u8 [planes, h, w], for the region of interest x0 <= x < x1, y0 <= y < y1 (inside the
+ * photograph, not empty): per ROI pixel (x - x0 + 0.5, y - y0 + 0.5) the source position of hf_quad_bilinear_u8's polynomial
+ * (coef8: HOST pointer to a0..a7) in the n x n source; m = the bilinear sample of mask u8 [n, n] there, 0 outside the
+ * source; where m != 0, per plane a = the bilinear sample of src u8 [planes, n, n], b = the photograph's byte,
+ * t = a m + b (255 - m) + 128, byte = ((t >> 8) + t) >> 8.  These are PIL's Image.transform((x1 - x0, y1 - y0), QUAD,
+ * BILINEAR) of src and of mask followed by Image.composite(warped, roi, warped mask).  Nothing outside the ROI is touched.
+ * HF_E_INVALID: a null pointer, a non-positive dimension, an empty ROI or one that leaves the photograph. */
+int hf_paste_quad_u8(unsigned char *photo, const unsigned char *src, const unsigned char *mask, const double *coef8, int planes,
+                     int h, int w, int n, int x0, int y0, int x1, int y1, void *stream);
+/* PIL ImageChops.multiply of two byte arrays of n elements: out = a * b / 255, rounded down (out: a buffer of its own). */
+int hf_multiply_u8(unsigned char *out, const unsigned char *a, const unsigned char *b, long long n, void *stream);
+
 /* ---- the PNG bytes of --save_all (utils/save_utils.py:12-30: ToPILImage, mask_to_rgb; csrc/export.h) ----
  * in: planar fp32 [batch, 3, h, w]; out: u8 [batch, h, w, 3] when `interleaved`, else [batch, 3, h, w].
  * t = (x - lo) / (hi - lo) ((lo, hi) = (-1, 1): (x + 1) / 2; (0, 1): t = x, nothing computed); then
