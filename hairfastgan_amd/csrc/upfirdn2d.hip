@@ -413,7 +413,7 @@ extern "C" int hf_blur_noise_bias_act_f32(float *out, const float *in, const flo
       (noise && !noise_w))
     return HF_E_INVALID;
   const long long planes = (long long)batch * channels;
-  if (planes > 65535LL * 32768) return HF_E_INVALID;
+  if (planes > 65535) return HF_E_INVALID;  // gridDim.z, as the split form below
   const int out_h = in_h - 1, out_w = in_w - 1;
   const bool aligned = ((((size_t)out) | ((size_t)noise)) & 15) == 0 && (noise_bstride & 3) == 0;
   if ((out_w & 3) == 0 && aligned) {

@@ -276,7 +276,8 @@ int hf_modconv_up_pitch(int w);
  * 77-93, called :263) + NoiseInjection + FusedLeakyReLU.  Rows of `in` are in_pitch floats
  * apart (in_pitch >= in_w; hf_modconv_up_pitch for the fused path).  kernel4x4: device
  * pointer to the module's `blur.kernel` buffer (already multiplied by
- * upsample_factor**2, model.py:83-84).  noise/bias NULL as in hf_modconv3x3_f32. */
+ * upsample_factor**2, model.py:83-84).  noise/bias NULL as in hf_modconv3x3_f32.
+ * batch * channels <= 65535 (the planes are the grid's z axis), else HF_E_INVALID. */
 int hf_blur_noise_bias_act_f32(float *out, const float *in, const float *kernel4x4, const float *noise,
                                const float *noise_w, long long noise_bstride, const float *bias,
                                int batch, int channels, int in_h, int in_w, int in_pitch, float alpha,
