@@ -17,6 +17,7 @@ import torch.nn.functional as F
 
 from hairfastgan_amd import _marshal as M
 from oracle import ref_stylegan2 as O
+from tests.conv_kernel_checks import presplit, styled_layer
 from tests.small_ops_checks import ROWS, SENTINEL, Case, _c, _guard_ok, _guarded, _offset_view, _sync, accuracy, exact, invariant  # noqa: F401
 
 ALPHA = float(torch.tensor(0.2, dtype=torch.float32))        # the fp32 values the kernels receive
@@ -377,44 +378,37 @@ def close(lib_is_sim, what, got, ref):
 
 
 def check_conv_route(lib, st, dev, case):
-    route, (B, cin, cout, H, W), kind = case.args
+    route, shape, kind = case.args
+    B, cin, cout, H, W = shape
     sim = dev.type == "cpu"
-    torch.manual_seed(212)
-    x, wgt = torch.randn(B, cin, H, W), torch.randn(1, cout, cin, 3, 3)
-    mw, mb, sty = torch.randn(cin, 16), torch.randn(cin), torch.randn(B, 16)
-    nz, nw, bias = torch.randn(B, 1, 2 * H, 2 * W), torch.tensor([0.3]), torch.randn(cout)
-    k = filt(kind)
-    full = O.fused_leaky_relu(O.modulated_conv2d(x.double(), sty.double(), wgt.double(), mw.double(), mb.double(), True, True,
-                                                 blur_kernel=k.double()) + nw.double() * nz.double(), bias.double())
-    xd, kd, nzd, nwd, bd = x.to(dev), k.to(dev), nz.to(dev), nw.to(dev), bias.to(dev)
-    wt, wsq = M.prepare_weights(lib, st, wgt.to(dev))
-    s = M.modulation(lib, st, sty.to(dev), mw.to(dev), mb.to(dev))
-    dm = M.demod(lib, st, s, wsq)
-    M.style_normalize(lib, st, s, dm)
+    L = styled_layer(lib, st, dev, shape, 212, True)
+    c, k = L.cpu, filt(kind)
+    full = O.fused_leaky_relu(O.modulated_conv2d(c.x.double(), c.sty.double(), c.wgt.double(), c.mw.double(), c.mb.double(), True, True,
+                                                 blur_kernel=k.double()) + c.nw.double() * c.nz.double(), c.bias.double())
+    kd, tail = k.to(dev), (L.nz, L.nw, L.bias)
+    M.style_normalize(lib, st, L.s, L.dm)
     if route == "fp32_up":
-        y = M.modconv3x3_up(lib, st, xd, wt, s, dm, kd, nzd, nwd, bd)
+        y = M.modconv3x3_up(lib, st, L.x, L.wt, L.s, L.dm, kd, *tail)
     elif route == "two_pass_f16":
-        hi, lo = M.split_weights_f16(lib, st, wt)
         assert M.modconv3x3_up_f16_supported(cin, cout, H, W)
-        y = M.modconv3x3_up(lib, st, xd, wt, s, dm, kd, nzd, nwd, bd, f16=(hi, lo, 3))
+        y = M.modconv3x3_up(lib, st, L.x, L.wt, L.s, L.dm, kd, *tail, f16=(L.hi, L.lo, 3))
         assert lib.hf_debug_last_path() == 563
     elif route == "fused":
-        hi, lo = M.split_weights_f16(lib, st, wt)
         fac = M.blur_factors(k)
         assert fac is not None and M.modconv3x3_up_fused_supported(cin, cout, H, W)
-        y = M.modconv3x3_up_fused(lib, st, xd, hi, lo, s, dm, fac, nzd, nwd, bd)
+        y = M.modconv3x3_up_fused(lib, st, L.x, L.hi, L.lo, L.s, L.dm, fac, *tail)
         assert lib.hf_debug_last_path() == 573
         s2 = (torch.rand(B, cout) + 0.5).to(dev)
-        sp = M.modconv3x3_up_fused(lib, st, xd, hi, lo, s, dm, fac, nzd, nwd, bd, split_for=s2)
+        sp = M.modconv3x3_up_fused(lib, st, L.x, L.hi, L.lo, L.s, L.dm, fac, *tail, split_for=s2)
         _sync(dev)
         eh, el = M.split_activation_reference(y.cpu(), s2.cpu())
         exact("conv_route", case.label + " split hi", sp.hi, eh)
         exact("conv_route", case.label + " split lo", sp.lo, el)
     else:
         assert route == "small_up_blur"
-        w9 = M.split_weights_small(lib, st, wt)
+        w9 = M.split_weights_small(lib, st, L.wt)
         assert M.small_up_blur_supported(H, W)
-        y = M.modconv3x3_small_up_blur(lib, st, xd, w9, 3, s, dm, kd, nzd, nwd, bd, cout)
+        y = M.modconv3x3_small_up_blur(lib, st, L.x, w9, 3, L.s, L.dm, kd, *tail, cout)
         assert lib.hf_debug_last_path() == 705
     _sync(dev)
     close(sim, f"conv_route {case.label}", y, full)
@@ -424,20 +418,12 @@ def check_rows_image(lib, st, dev, case):
     """The row pipeline's image epilogue (skip ring): hf_modconv3x3_f16_pre_image_f32 with the filter equals the raw product plus
     hf_torgb_f32's finishing pass with the same filter (itself checked against fp64 by check_torgb), bit for bit."""
     (B, H, W), kind = case.args
-    torch.manual_seed(213)
-    cin = cout = 32
-    x, wgt = torch.randn(B, cin, H, W), torch.randn(1, cout, cin, 3, 3)
-    s, dm = torch.rand(B, cin) + 0.5, (torch.rand(B, cout) + 0.5).to(dev)
-    nz, nw, bias = torch.randn(B, 1, H, W).to(dev), torch.tensor([0.3]).to(dev), torch.randn(cout).to(dev)
-    rgb_w, rgb_s = (torch.randn(cout, 3) * 0.2).to(dev), (torch.rand(B, cout) + 0.5).to(dev)
-    skip, rgb_bias, k = (torch.randn(B, 3, H // 2, W // 2) + 1.0).to(dev), torch.randn(1, 3, 1, 1).to(dev), filt(kind).to(dev)
-    wt, _ = M.prepare_weights(lib, st, wgt.to(dev))
-    hi, lo = M.split_weights_f16(lib, st, wt)
-    xh, xl = M.split_activation_reference(x, s)
-    act = M.SplitActivation(xh.to(dev), xl.to(dev), None)
-    _, raw = M.modconv3x3_f16_pre(lib, st, act, hi, lo, 3, dm, nz, nw, bias, rgb=(rgb_w, rgb_s))
+    L = styled_layer(lib, st, dev, (B, 32, 32, H, W), 213, False, rgb=True)
+    skip, rgb_bias, k = L.skip + 1.0, L.brgb.view(1, 3, 1, 1), filt(kind).to(dev)
+    conv = (presplit(L), L.hi, L.lo, 3, L.dm, L.nz, L.nw, L.bias)
+    _, raw = M.modconv3x3_f16_pre(lib, st, *conv, rgb=(L.wtr, L.sr))
     want = M.torgb(lib, st, raw, torch.eye(3).reshape(1, 3, 3).to(dev), None, rgb_bias, skip, k)
-    img = M.modconv3x3_f16_pre_image(lib, st, act, hi, lo, 3, dm, nz, nw, bias, (rgb_w, rgb_s), rgb_bias, skip, k)
+    img = M.modconv3x3_f16_pre_image(lib, st, *conv, (L.wtr, L.sr), rgb_bias, skip, k)
     assert img is not None and lib.hf_debug_last_path() == 579
     _sync(dev)
     exact("rows_image", case.label, img, want.cpu())

@@ -68,8 +68,9 @@ def accuracy(op, label, got, ref64, t32, factor=FACTOR):
 
 
 def exact(op, label, got, want):
+    """Equal bits, compared on the device that holds `got` (a conv check's activation can be 1 GB)."""
     _sync(got.device)
-    assert got.shape == want.shape and torch.equal(got.cpu(), want), (op, label)
+    assert got.shape == want.shape and torch.equal(got, want.to(got.device)), (op, label)
 
 
 def _guarded(n, dev):

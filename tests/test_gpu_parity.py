@@ -7,6 +7,9 @@ modulation applied to activations, demodulation to outputs), so results differ f
 reference's ATen kernels at fp32 round-off: we require max-abs <= 1e-4 * max(1, |ref|max)
 and MSE <= 1e-8 * max(1, var) (SURVEY.md section 8c measured the reference's own
 fp32-vs-fp64 noise floor at 8.9e-6 max-abs); north_star's pixel-MSE bar is 1e-4.
+
+The kernel-level conv checks are stated once, in tests/conv_kernel_checks.py, for this file and for
+tests/test_sim_kernels.py; their tests here are one call each.
 """
 import numpy as np
 import pytest
@@ -14,6 +17,7 @@ import torch
 
 from oracle import cases as C
 from oracle import ref_stylegan2 as O
+from tests import conv_kernel_checks as K
 
 pytestmark = pytest.mark.gpu
 
@@ -24,6 +28,14 @@ def _dev():
     if not torch.cuda.is_available():
         pytest.fail("-m gpu tests need a GPU (torch.cuda.is_available() is False)")
     return torch.device("cuda:0")
+
+
+def _native():
+    """(library, stream, device) of the checks in tests/conv_kernel_checks.py."""
+    dev = _dev()
+    from hairfastgan_amd._runtime import lib, stream
+
+    return lib(), stream(), dev
 
 
 def close(y, ref, rel=REL):
@@ -100,30 +112,7 @@ def test_small_modules_vs_reference_golden(golden, name):
 
 
 def test_modconv_tile_geometries_vs_oracle():
-    """Ragged / tiny / odd shapes: multi-image tiles, partial tiles, cout % 32 != 0,
-    cout % 4 != 0, cin % 8 != 0, 1-pixel planes, and each kernel instantiation."""
-    from hairfastgan_amd import _marshal as M
-    from hairfastgan_amd._runtime import lib, stream
-
-    dev = _dev()
-    torch.manual_seed(1)
-    shapes = [(3, 8, 8, 4, 4), (1, 12, 34, 40, 72), (2, 16, 33, 9, 5), (5, 8, 64, 2, 2), (1, 8, 8, 1, 1),
-              (2, 64, 128, 72, 72), (1, 128, 64, 130, 66), (9, 32, 32, 32, 32), (2, 40, 256, 16, 16)]
-    for (B, cin, cout, H, W) in shapes:
-        x = torch.randn(B, cin, H, W)
-        wgt = torch.randn(1, cout, cin, 3, 3)
-        mw, mb, sty = torch.randn(cin, 16), torch.randn(cin), torch.randn(B, 16)
-        wt, wsq = M.prepare_weights(lib(), stream(), wgt.to(dev))
-        s = M.modulation(lib(), stream(), sty.to(dev), mw.to(dev), mb.to(dev))
-        dm = M.demod(lib(), stream(), s, wsq)
-        for up in (False, True):
-            ref = O.modulated_conv2d(x, sty, wgt, mw, mb, True, up)
-            if up:
-                y = M.modconv3x3_up(lib(), stream(), x.to(dev), wt, s, dm, O.blur_kernel_1d_to_2d(gain=4.0).to(dev),
-                                    None, None, None)
-            else:
-                y = M.modconv3x3(lib(), stream(), x.to(dev), wt, s, dm, None, None, None)
-            close(y, ref)
+    K.run_all("tile_geometries", *_native())
 
 
 def _gpu_generator(tag, dev):
@@ -262,188 +251,29 @@ def test_random_noise_path_statistics():
     assert torch.equal(a, a2)
 
 
-@pytest.mark.parametrize("cfg,shape", [
-    (11, (2, 64, 128, 40, 64)), (12, (1, 32, 64, 24, 40)), (13, (2, 16, 32, 48, 96)), (14, (1, 32, 128, 8, 32)),
-    (15, (2, 16, 64, 8, 8)), (16, (1, 16, 32, 32, 64)),
-    (31, (2, 64, 128, 40, 64)), (32, (1, 32, 64, 24, 64)), (33, (2, 16, 32, 44, 96)), (34, (1, 32, 128, 12, 32)),
-    (21, (2, 32, 64, 8, 32)), (22, (1, 16, 32, 16, 32)), (23, (1, 16, 64, 6, 40)), (24, (1, 32, 64, 16, 32)),
-    (25, (2, 16, 32, 4, 32)),
-])
-def test_every_pipelined_instantiation_vs_oracle(cfg, shape):
-    """Each double-buffered kernel instantiation (register-staged, DMA-staged, transposed),
-    forced through hf_debug_set_dispatch, on shapes with ragged tiles - and the assertion
-    that the forced kernel really ran (no silent fallback to the general kernel)."""
-    from hairfastgan_amd import _marshal as M
-    from hairfastgan_amd._runtime import lib, stream
-
-    dev = _dev()
-    B, cin, cout, H, W = shape
-    torch.manual_seed(cfg)
-    x = torch.randn(B, cin, H, W)
-    wgt = torch.randn(1, cout, cin, 3, 3)
-    mw, mb, sty = torch.randn(cin, 16), torch.randn(cin), torch.randn(B, 16)
-    wt, wsq = M.prepare_weights(lib(), stream(), wgt.to(dev))
-    s = M.modulation(lib(), stream(), sty.to(dev), mw.to(dev), mb.to(dev))
-    dm = M.demod(lib(), stream(), s, wsq)
-    up = 20 <= cfg < 30
-    ref = O.modulated_conv2d(x, sty, wgt, mw, mb, True, up)
-    try:
-        lib().hf_debug_set_dispatch(0 if up else cfg, cfg if up else 0)
-        if up:
-            y = M.modconv3x3_up(lib(), stream(), x.to(dev), wt, s, dm, O.blur_kernel_1d_to_2d(gain=4.0).to(dev), None, None, None)
-        else:
-            y = M.modconv3x3(lib(), stream(), x.to(dev), wt, s, dm, None, None, None)
-        assert lib().hf_debug_last_path() == 200 + cfg
-    finally:
-        lib().hf_debug_set_dispatch(0, 0)
-    close(y, ref)
+@pytest.mark.parametrize("case", K.params("pipelined", gpu=True))
+def test_every_pipelined_instantiation_vs_oracle(case):
+    K.check_pipelined(*_native(), case)
 
 
-@pytest.mark.parametrize("nterms,tol", [(3, 5e-6), (1, 4e-3)])
-@pytest.mark.parametrize("shape", [(2, 64, 64, 32, 32), (1, 48, 128, 20, 70), (2, 512, 512, 64, 64), (1, 32, 32, 100, 64)])
-def test_modconv_f16_matrix_cores(nterms, tol, shape):
-    """csrc/convh.hip against the exact-fp32 MFMA kernel and (small shapes) the oracle:
-    split fp16 operands = fp32-class accuracy, plain fp16 = operand rounding only."""
-    from hairfastgan_amd import _marshal as M
-    from hairfastgan_amd._runtime import lib as _lib_fn, stream
-
-    B, cin, cout, H, W = shape
-    torch.manual_seed(7)
-    dev = _dev()
-    lib = _lib_fn()
-    x = torch.randn(B, cin, H, W, device=dev)
-    wgt = torch.randn(1, cout, cin, 3, 3, device=dev)
-    mw, mb, sty = torch.randn(cin, 16, device=dev), torch.randn(cin, device=dev), torch.randn(B, 16, device=dev)
-    nz, nw, bias = torch.randn(B, 1, H, W, device=dev), torch.tensor([0.3], device=dev), torch.randn(cout, device=dev)
-    st = stream()
-    wt, wsq = M.prepare_weights(lib, st, wgt)
-    s = M.modulation(lib, st, sty, mw, mb)
-    dm = M.demod(lib, st, s, wsq)
-    hi, lo = M.split_weights_f16(lib, st, wt)
-    ref = M.modconv3x3(lib, st, x, wt, s, dm, nz, nw, bias)
-    y = M.modconv3x3_f16(lib, st, x, hi, lo, nterms, s, dm, nz, nw, bias)
-    torch.cuda.synchronize()
-    scale = max(1.0, float(ref.abs().max()))
-    assert float((y - ref).abs().max()) < tol * scale
-    if cin <= 64:
-        full = O.fused_leaky_relu(O.modulated_conv2d(x.cpu(), sty.cpu(), wgt.cpu(), mw.cpu(), mb.cpu(), True, False)
-                                  + nw.cpu() * nz.cpu(), bias.cpu())
-        assert float((y.cpu() - full).abs().max()) < (1e-5 if nterms == 3 else tol) * scale
+@pytest.mark.parametrize("case", K.params("f16_matrix_cores", gpu=True))
+def test_modconv_f16_matrix_cores(case):
+    K.check_f16_matrix_cores(*_native(), case)
 
 
-@pytest.mark.parametrize("nterms,tol", [(3, 5e-6), (1, 4e-3)])
-@pytest.mark.parametrize("shape", [(2, 64, 64, 16, 16), (1, 48, 128, 20, 70), (2, 512, 256, 64, 64), (1, 64, 32, 40, 64)])
-def test_modconv_up_f16_matrix_cores(nterms, tol, shape):
-    """Transposed conv of csrc/convh.hip (interior + rim tile families) + blur epilogue against
-    the exact-fp32 MFMA path and (small shapes) the oracle."""
-    from hairfastgan_amd import _marshal as M
-    from hairfastgan_amd._runtime import lib as _lib_fn, stream
-
-    B, cin, cout, H, W = shape
-    torch.manual_seed(11)
-    dev = _dev()
-    lib = _lib_fn()
-    x = torch.randn(B, cin, H, W, device=dev)
-    wgt = torch.randn(1, cout, cin, 3, 3, device=dev)
-    mw, mb, sty = torch.randn(cin, 16, device=dev), torch.randn(cin, device=dev), torch.randn(B, 16, device=dev)
-    nz, nw, bias = torch.randn(B, 1, 2 * H, 2 * W, device=dev), torch.tensor([0.3], device=dev), torch.randn(cout, device=dev)
-    st = stream()
-    wt, wsq = M.prepare_weights(lib, st, wgt)
-    s = M.modulation(lib, st, sty, mw, mb)
-    dm = M.demod(lib, st, s, wsq)
-    hi, lo = M.split_weights_f16(lib, st, wt)
-    k4 = O.blur_kernel_1d_to_2d(gain=4.0).to(dev)
-    assert M.modconv3x3_up_f16_supported(cin, cout, H, W)
-    ref = M.modconv3x3_up(lib, st, x, wt, s, dm, k4, nz, nw, bias)
-    y = M.modconv3x3_up(lib, st, x, wt, s, dm, k4, nz, nw, bias, f16=(hi, lo, nterms))
-    assert lib.hf_debug_last_path() in (561, 563)
-    torch.cuda.synchronize()
-    scale = max(1.0, float(ref.abs().max()))
-    assert float((y - ref).abs().max()) < tol * scale
-    if cin <= 64:
-        full = O.fused_leaky_relu(O.modulated_conv2d(x.cpu(), sty.cpu(), wgt.cpu(), mw.cpu(), mb.cpu(), True, True)
-                                  + nw.cpu() * nz.cpu(), bias.cpu())
-        assert float((y.cpu() - full).abs().max()) < (1e-5 if nterms == 3 else tol) * scale
+@pytest.mark.parametrize("case", K.params("up_f16_matrix_cores", gpu=True))
+def test_modconv_up_f16_matrix_cores(case):
+    K.check_up_f16_matrix_cores(*_native(), case)
 
 
-@pytest.mark.parametrize("up", [False, True])
-@pytest.mark.parametrize("blocks,shape", [(0, (3, 64, 64, 64, 96)), (7, (3, 64, 64, 64, 96)), (64, (3, 64, 64, 64, 96)),
-                                          (4, (9, 32, 64, 16, 32))])  # last: a new image on every tile step
-def test_modconv_f16_persistent_tile_walk(up, blocks, shape):
-    """Resident blocks walking many tiles (csrc/convh.hip): same result for any block count,
-    equal to the exact-fp32 MFMA path; B=3 crosses images, the transposed conv crosses families."""
-    from hairfastgan_amd import _marshal as M
-    from hairfastgan_amd._runtime import lib as _lib_fn, stream
-
-    B, cin, cout, H, W = shape
-    torch.manual_seed(5)
-    dev = _dev()
-    lib = _lib_fn()
-    st = stream()
-    x = torch.randn(B, cin, H, W, device=dev)
-    wgt = torch.randn(1, cout, cin, 3, 3, device=dev)
-    mw, mb, sty = torch.randn(cin, 16, device=dev), torch.randn(cin, device=dev), torch.randn(B, 16, device=dev)
-    oh, ow = (2 * H, 2 * W) if up else (H, W)
-    nz, nw, bias = torch.randn(B, 1, oh, ow, device=dev), torch.tensor([0.3], device=dev), torch.randn(cout, device=dev)
-    wt, wsq = M.prepare_weights(lib, st, wgt)
-    s = M.modulation(lib, st, sty, mw, mb)
-    dm = M.demod(lib, st, s, wsq)
-    hi, lo = M.split_weights_f16(lib, st, wt)
-    k4 = O.blur_kernel_1d_to_2d(gain=4.0).to(dev)
-    if up:
-        ref = M.modconv3x3_up(lib, st, x, wt, s, dm, k4, nz, nw, bias)
-    else:
-        ref = M.modconv3x3(lib, st, x, wt, s, dm, nz, nw, bias)
-    try:
-        lib.hf_debug_set_persistent_blocks(blocks)
-        first = None
-        for _ in range(4):  # repeated: bit-identical results (no LDS slot races between waves)
-            if up:
-                y = M.modconv3x3_up(lib, st, x, wt, s, dm, k4, nz, nw, bias, f16=(hi, lo, 3))
-            else:
-                y = M.modconv3x3_f16(lib, st, x, hi, lo, 3, s, dm, nz, nw, bias)
-            torch.cuda.synchronize()
-            assert float((y - ref).abs().max()) < 5e-6 * max(1.0, float(ref.abs().max()))
-            first = y.clone() if first is None else first
-            assert torch.equal(y, first)
-    finally:
-        lib.hf_debug_set_persistent_blocks(0)
+@pytest.mark.parametrize("case", K.params("persistent_tile_walk", gpu=True))
+def test_modconv_f16_persistent_tile_walk(case):
+    K.check_persistent_tile_walk(*_native(), case)
 
 
-@pytest.mark.parametrize("shape", [(2, 64, 64, 64, 64), (1, 32, 32, 96, 128), (2, 256, 256, 64, 64), (1, 64, 96, 32, 64)])
-def test_modconv_f16_fused_torgb(shape):
-    """Fused ToRGB epilogue (hf_modconv3x3_f16_rgb_f32) + finishing pass == conv followed by the
-    stand-alone ToRGB kernel; the conv output itself is unchanged bit for bit."""
-    from hairfastgan_amd import _marshal as M
-    from hairfastgan_amd._runtime import lib as _lib_fn, stream
-
-    B, cin, cout, H, W = shape
-    torch.manual_seed(9)
-    dev = _dev()
-    lib, st = _lib_fn(), stream()
-    r = lambda *sz: torch.randn(*sz, device=dev)  # noqa: E731
-    x, wgt = r(B, cin, H, W), r(1, cout, cin, 3, 3)
-    mw, mb, sty = r(cin, 16), r(cin), r(B, 16)
-    nz, nw, bias = r(B, 1, H, W), torch.tensor([0.3], device=dev), r(cout)
-    wrgb, mwr, mbr, styr = r(1, 3, cout, 1, 1), r(cout, 16), r(cout), r(B, 16)
-    brgb, skip = r(3), r(B, 3, H // 2, W // 2)
-    wt, wsq = M.prepare_weights(lib, st, wgt)
-    s = M.modulation(lib, st, sty, mw, mb)
-    dm = M.demod(lib, st, s, wsq)
-    hi, lo = M.split_weights_f16(lib, st, wt)
-    wtr, _ = M.prepare_weights(lib, st, wrgb)
-    sr = M.modulation(lib, st, styr, mwr, mbr)
-    k4 = O.blur_kernel_1d_to_2d(gain=4.0).to(dev)
-    assert M.modconv3x3_f16_supported(cin, cout, H, W) and cout % 32 == 0  # what the kernel takes (torgb_fusable: the policy)
-    y, raw = M.modconv3x3_f16(lib, st, x, hi, lo, 3, s, dm, nz, nw, bias, rgb=(wtr, sr))
-    y_plain = M.modconv3x3_f16(lib, st, x, hi, lo, 3, s, dm, nz, nw, bias)
-    slabs = M.torgb_slabs(cout)  # one partial sum per 64 (32) output channels, added by the finishing pass
-    assert raw.shape == (B, 3 * slabs, H, W)
-    rgb = M.torgb(lib, st, raw, torch.eye(3, device=dev).repeat(slabs, 1).reshape(1, 3 * slabs, 3), None, brgb, skip, k4)
-    ref = M.torgb(lib, st, y, wtr, sr, brgb, skip, k4)
-    torch.cuda.synchronize()
-    assert torch.equal(y, y_plain)
-    assert float((rgb - ref).abs().max()) < 2e-5 * max(1.0, float(ref.abs().max()))
+@pytest.mark.parametrize("case", K.params("fused_torgb", gpu=True))
+def test_modconv_f16_fused_torgb(case):
+    K.check_fused_torgb(*_native(), case)
 
 
 def test_generator1024_fuses_torgb_of_the_top_layers(monkeypatch):
@@ -569,47 +399,14 @@ def test_generator1024_other_precision_modes(golden, mode, bar):
     print(f"{mode}: crop mse {mse:.3e}, strided-sample mse {mse_s:.3e}")
 
 
-@pytest.mark.parametrize("shape", [(2, 64, 64, 32, 32), (1, 48, 128, 20, 70), (2, 512, 512, 64, 64), (1, 32, 32, 100, 128),
-                                   (9, 32, 64, 16, 32)])
-def test_modconv_f16_presplit_pipeline(shape):
-    """Producer-side split: hf_blur_noise_bias_act_split_f16 -> hf_modconv3x3_f16_pre_f32 equals
-    hf_blur_noise_bias_act_f32 -> hf_modconv3x3_f16_f32 bit for bit (activations by LDS-DMA instead of
-    per-element loads + in-kernel split), repeated launches identical."""
-    from hairfastgan_amd import _marshal as M
-    from hairfastgan_amd._runtime import lib as _lib_fn, stream
+@pytest.mark.parametrize("case", K.params("presplit_input", gpu=True))
+def test_modconv_f16_presplit_pipeline(case):
+    K.check_presplit_input(*_native(), case)
 
-    B, cin, cout, H, W = shape  # H, W: resolution of the same-res conv = output of the blur
-    torch.manual_seed(21)
-    dev = _dev()
-    lib, st = _lib_fn(), stream()
-    r = lambda *sz: torch.randn(*sz, device=dev)  # noqa: E731
-    h2, w2 = H // 2, W // 2
-    pitch = lib.hf_modconv_up_pitch(w2)
-    tmp = r(B, cin, 2 * h2 + 1, pitch)
-    k4 = O.blur_kernel_1d_to_2d(gain=4.0).to(dev)
-    nz1, nw1, b1 = r(B, 1, 2 * h2, 2 * w2), torch.tensor([0.2], device=dev), r(cin)
-    wgt = r(1, cout, cin, 3, 3)
-    s, dm = torch.rand(B, cin, device=dev) + 0.5, torch.rand(B, cout, device=dev) + 0.5
-    nz2, nw2, b2 = r(B, 1, 2 * h2, 2 * w2), torch.tensor([0.3], device=dev), r(cout)
-    wt, _ = M.prepare_weights(lib, st, wgt)
-    hi, lo = M.split_weights_f16(lib, st, wt)
-    x = torch.empty(B, cin, 2 * h2, 2 * w2, device=dev)
-    M.check(lib, lib.hf_blur_noise_bias_act_f32(x.data_ptr(), tmp.data_ptr(), k4.data_ptr(), nz1.data_ptr(), nw1.data_ptr(),
-                                                4 * h2 * w2, b1.data_ptr(), B, cin, 2 * h2 + 1, 2 * w2 + 1, pitch, 0.2, 2 ** 0.5, st),
-            "blur")
-    xh = torch.empty(B, cin // 8, 2 * h2, 2 * w2, 8, dtype=torch.float16, device=dev)
-    xl = torch.empty_like(xh)
-    M.check(lib, lib.hf_blur_noise_bias_act_split_f16(xh.data_ptr(), xl.data_ptr(), tmp.data_ptr(), k4.data_ptr(), nz1.data_ptr(),
-                                                      nw1.data_ptr(), 4 * h2 * w2, b1.data_ptr(), s.data_ptr(), B, cin, 2 * h2 + 1,
-                                                      2 * w2 + 1, pitch, 0.2, 2 ** 0.5, st), "blur split")
-    eh, el = M.split_activation_reference(x, s)
-    torch.cuda.synchronize()
-    assert torch.equal(xh, eh) and torch.equal(xl, el)
-    ref = M.modconv3x3_f16(lib, st, x, hi, lo, 3, s, dm, nz2, nw2, b2)
-    for _ in range(3):
-        y = M.modconv3x3_f16_pre(lib, st, M.SplitActivation(xh, xl, None), hi, lo, 3, dm, nz2, nw2, b2)
-        torch.cuda.synchronize()
-        assert torch.equal(y, ref)
+
+@pytest.mark.parametrize("case", K.params("presplit_chain", gpu=True))
+def test_presplit_chain_same_res_to_transposed(case):
+    K.check_presplit_chain(*_native(), case)
 
 
 def test_generator1024_fast_paths_equal_the_module_by_module_path():
@@ -638,76 +435,13 @@ def test_generator1024_fast_paths_equal_the_module_by_module_path():
 # Range of the fp16 (hi, lo) operand split (round-1 verdict / advisor: the default f16x3 mode must
 # not depend on tame O(1) tensors)
 # ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("sty_scale,x_scale", [(1e5, 1.0), (1e-5, 1.0), (1.0, 5e3), (1.0, 1e-2), (1.0, 1e-4), (1e4, 5e3),
-                                               (1e3, 1e3), (1e-3, 1e-3)])
-def test_f16_split_range(sty_scale, x_scale):
-    """f16x3 against the exact-fp32 MFMA kernel with styles / activations scaled by 1e+-2 ... 1e+-5:
-    styles are normalised away exactly (hf_style_normalize_f32), weights are pre-scaled into the
-    normal fp16 range, both split parts saturate; the error follows the model of
-    include/hairfast_hip.h (2^-22 relative per operand, 2^-25 absolute once |s*x| < 2^-3)."""
-    from hairfastgan_amd import _marshal as M
-    from hairfastgan_amd._runtime import lib as _lib_fn, stream
-
-    dev = _dev()
-    lib, st = _lib_fn(), stream()
-    B, cin, cout, H, W = 2, 128, 128, 64, 64
-    torch.manual_seed(3)
-    wgt = torch.randn(1, cout, cin, 3, 3, device=dev)
-    mw, mb, sty = torch.randn(cin, 16, device=dev), torch.randn(cin, device=dev), torch.randn(B, 16, device=dev)
-    wt, wsq = M.prepare_weights(lib, st, wgt)
-    hi, lo = M.split_weights_f16(lib, st, wt)
-    x = torch.randn(B, cin, H, W, device=dev) * x_scale
-    M.f16_overflow_count(lib, reset=True)
-    s = M.modulation(lib, st, sty * sty_scale, mw, mb * sty_scale)
-    dm = M.demod(lib, st, s, wsq)
-    s0, d0 = s.clone(), dm.clone()
-    M.style_normalize(lib, st, s, dm)
-    assert 1.0 <= float(s.abs().amax(1).min()) and float(s.abs().amax(1).max()) < 2.0
-    # exact power-of-two rescaling: the fp32 kernel returns the very same bits with either pair
-    ref0 = M.modconv3x3(lib, st, x, wt, s0, d0, None, None, None)
-    ref = M.modconv3x3(lib, st, x, wt, s, dm, None, None, None)
-    assert torch.equal(ref, ref0)
-    y = M.modconv3x3_f16(lib, st, x, hi, lo, 3, s, dm, None, None, None)
-    # the producer-side split (what the generator's fast path uses) + the pre-split consumer
-    xh, xl = M.split_activation_reference(x, s)
-    y_pre = M.modconv3x3_f16_pre(lib, st, M.SplitActivation(xh, xl, None), hi, lo, 3, dm, None, None, None)
-    torch.cuda.synchronize()
-    assert torch.isfinite(y).all() and torch.isfinite(y_pre).all()
-    tol = 5e-6 + 6e-8 / min(1.0, x_scale)
-    scale = float(ref.abs().max())
-    assert float((y - ref).abs().max()) < tol * scale, float((y - ref).abs().max()) / scale
-    assert float((y_pre - ref).abs().max()) < tol * scale
-    assert M.f16_overflow_count(lib) == 0
+@pytest.mark.parametrize("case", K.params("f16_split_range", gpu=True))
+def test_f16_split_range(case):
+    K.check_f16_split_range(*_native(), case)
 
 
 def test_f16_split_saturates_and_counts():
-    """Activations beyond the fp16-pair range: no inf / NaN, the clamp counter reports it (so a
-    caller can fall back to the f32 kernels), and the counter resets."""
-    from hairfastgan_amd import _marshal as M
-    from hairfastgan_amd._runtime import lib as _lib_fn, stream
-
-    dev = _dev()
-    lib, st = _lib_fn(), stream()
-    B, cin, cout, H, W = 1, 64, 64, 32, 32
-    torch.manual_seed(5)
-    wgt = torch.randn(1, cout, cin, 3, 3, device=dev)
-    mw, mb, sty = torch.randn(cin, 16, device=dev), torch.randn(cin, device=dev), torch.randn(B, 16, device=dev)
-    wt, wsq = M.prepare_weights(lib, st, wgt)
-    hi, lo = M.split_weights_f16(lib, st, wt)
-    s = M.modulation(lib, st, sty, mw, mb)
-    dm = M.demod(lib, st, s, wsq)
-    M.style_normalize(lib, st, s, dm)
-    x = torch.randn(B, cin, H, W, device=dev) * 2e5
-    M.f16_overflow_count(lib, reset=True)
-    y = M.modconv3x3_f16(lib, st, x, hi, lo, 3, s, dm, None, None, None)
-    assert torch.isfinite(y).all()
-    assert M.f16_overflow_count(lib, reset=True) > 0
-    assert M.f16_overflow_count(lib) == 0
-    # the blur pass that writes a split activation saturates too
-    k4 = O.blur_kernel_1d_to_2d(gain=4.0).to(dev)
-    big = M.modconv3x3_up(lib, st, x, wt, s, dm, k4, None, None, None, f16=(hi, lo, 3), split_for=(None, s, True))
-    assert torch.isfinite(big.hi.float()).all() and torch.isfinite(big.lo.float()).all()
-    assert M.f16_overflow_count(lib, reset=True) > 0
+    K.run_all("f16_split_saturates", *_native())
 
 
 @pytest.mark.parametrize("scale", [1e3, 1e-3])
@@ -835,49 +569,18 @@ def test_ops_refuse_autograd():
 # ------------------------------------------------------------------------------------------------
 # The upsampling StyledConv as ONE kernel (transposed conv + blur + noise + bias + lrelu; no (2h+1)^2 intermediate)
 # ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape", [(2, 64, 32, 512, 512), (2, 128, 64, 256, 256), (1, 256, 128, 128, 128), (3, 32, 32, 75, 100),
-                                   (1, 512, 256, 64, 64)])
-def test_modconv_up_fused_blur(shape):
-    """hf_modconv3x3_up_blur_f16_f32 against the two-pass path (hf_modconv3x3_up_f16_f32 + blur pass) on the
-    generator's real layer shapes: same MFMA products, the separable blur only reassociates the 16-tap sum
-    (<= 2e-6 relative); the split output equals the split of the fused fp32 output bit for bit; pre-split
-    input equals fp32 input bit for bit; repeatable."""
-    from hairfastgan_amd import _marshal as M
-    from hairfastgan_amd._runtime import lib as _lib_fn, stream
+@pytest.mark.parametrize("case", K.params("up_fused_blur", gpu=True))
+def test_modconv_up_fused_blur(case):
+    K.check_up_fused_blur(*_native(), case)
 
-    B, cin, cout, H, W = shape
-    torch.manual_seed(13)
-    dev = _dev()
-    lib, st = _lib_fn(), stream()
-    x = torch.randn(B, cin, H, W, device=dev)
-    wgt = torch.randn(1, cout, cin, 3, 3, device=dev)
-    mw, mb, sty = torch.randn(cin, 16, device=dev), torch.randn(cin, device=dev), torch.randn(B, 16, device=dev)
-    nz, nw, bias = torch.randn(B, 1, 2 * H, 2 * W, device=dev), torch.tensor([0.3], device=dev), torch.randn(cout, device=dev)
-    wt, wsq = M.prepare_weights(lib, st, wgt)
-    s = M.modulation(lib, st, sty, mw, mb)
-    dm = M.demod(lib, st, s, wsq)
-    M.style_normalize(lib, st, s, dm)
-    hi, lo = M.split_weights_f16(lib, st, wt)
-    k4 = O.blur_kernel_1d_to_2d(gain=4.0).to(dev)
-    fac = M.blur_factors(k4)
-    ref = M.modconv3x3_up(lib, st, x, wt, s, dm, k4, nz, nw, bias, f16=(hi, lo, 3))
-    y = M.modconv3x3_up_fused(lib, st, x, hi, lo, s, dm, fac, nz, nw, bias)
-    assert lib.hf_debug_last_path() == 573
-    scale = max(1.0, float(ref.abs().max()))
-    assert float((y - ref).abs().max()) < 2e-6 * scale
-    assert torch.equal(y, M.modconv3x3_up_fused(lib, st, x, hi, lo, s, dm, fac, nz, nw, bias))
-    s2 = torch.rand(B, cout, device=dev) + 0.5
-    sp = M.modconv3x3_up_fused(lib, st, x, hi, lo, s, dm, fac, nz, nw, bias, split_for=s2)
-    eh, el = M.split_activation_reference(y, s2)
-    assert torch.equal(sp.hi, eh) and torch.equal(sp.lo, el)
-    xh, xl = M.split_activation_reference(x, s)
-    y3 = M.modconv3x3_up_fused(lib, st, M.SplitActivation(xh, xl, None), hi, lo, None, dm, fac, nz, nw, bias)
-    assert lib.hf_debug_last_path() == 593
-    assert torch.equal(y3, y)
-    if cin <= 64 and H * W <= 10000:
-        full = O.fused_leaky_relu(O.modulated_conv2d(x.cpu(), sty.cpu(), wgt.cpu(), mw.cpu(), mb.cpu(), True, True)
-                                  + nw.cpu() * nz.cpu(), bias.cpu())
-        assert float((y.cpu() - full).abs().max()) < 1e-5 * scale
+
+def test_modconv_up_fused_blur_plain_fp16_operands():
+    K.run_all("up_fused_blur_plain_fp16", *_native())
+
+
+@pytest.mark.parametrize("case", K.params("up_fused_blur_persistent", gpu=True))
+def test_modconv_up_fused_blur_persistent_walk(case):
+    K.check_up_fused_blur_persistent(*_native(), case)
 
 
 def test_auto_precision_reruns_clamped_forward_in_f32():
@@ -914,53 +617,9 @@ def test_auto_precision_reruns_clamped_forward_in_f32():
     assert _runtime.configured_conv_precision() != "auto" and _runtime.conv_precision() in ("f16x3", "f32", "f16")
 
 
-@pytest.mark.parametrize("B,H,W", [(8, 1024, 1024), (1, 1024, 1024), (3, 256, 192)])
-def test_conv_rows_pipeline_equals_tiled_kernel_on_hardware(B, H, W):
-    """csrc/convrow.hip at BASELINE.json's full size: the row pipeline (weights in registers, 18-slot LDS ring refilled
-    by LDS-DMA while the previous rows are read) against the tiled kernel (hf_debug_set_tuning bit 4), bit for bit, three
-    launches each - a ring slot overwritten too early or read too early shows up as a mismatch - and against the fp32-MFMA
-    kernel within the f16x3 tolerance."""
-    from hairfastgan_amd import _marshal as M
-    from hairfastgan_amd._runtime import lib as _lib_fn, stream
-
-    dev = _dev()
-    lib, st = _lib_fn(), stream()
-    torch.manual_seed(B + W)
-    r = lambda *sz: torch.randn(*sz, device=dev)  # noqa: E731
-    cin = cout = 32
-    x, wgt = r(B, cin, H, W), r(1, cout, cin, 3, 3)
-    s, dm = torch.rand(B, cin, device=dev) + 0.5, torch.rand(B, cout, device=dev) + 0.5
-    nz, nw, bias = r(B, 1, H, W), torch.tensor([0.3], device=dev), r(cout)
-    rgb_w, rgb_s = r(cout, 3) * 0.2, torch.rand(B, cout, device=dev) + 0.5
-    wt, _ = M.prepare_weights(lib, st, wgt)
-    hi, lo = M.split_weights_f16(lib, st, wt)
-    xh, xl = M.split_activation_reference(x, s)
-    act = M.SplitActivation(xh, xl, None)
-    try:
-        lib.hf_debug_set_tuning(16)
-        ref_out, ref_raw = M.modconv3x3_f16_pre(lib, st, act, hi, lo, 3, dm, nz, nw, bias, rgb=(rgb_w, rgb_s))
-        assert lib.hf_debug_last_path() in (573, 575)
-    finally:
-        lib.hf_debug_set_tuning(0)
-    for _ in range(3):
-        out, raw = M.modconv3x3_f16_pre(lib, st, act, hi, lo, 3, dm, nz, nw, bias, rgb=(rgb_w, rgb_s))
-        assert lib.hf_debug_last_path() == 579
-        torch.cuda.synchronize()
-        assert torch.equal(out, ref_out) and torch.equal(raw, ref_raw)
-    only_raw = M.modconv3x3_f16_pre(lib, st, act, hi, lo, 3, dm, nz, nw, bias, rgb=(rgb_w, rgb_s), want_out=False)[1]
-    assert torch.equal(only_raw, ref_raw)
-    # round 6 (ABI 13): the epilogue finishes ToRGB - bias + upsampled skip from a 16-row LDS ring of skip rows - against the raw
-    # product + hf_torgb_f32's finishing launch, bit for bit, three launches
-    skip, rgb_bias, k4 = r(B, 3, H // 2, W // 2), r(1, 3, 1, 1), O.blur_kernel_1d_to_2d(gain=4.0).to(dev)
-    want_img = M.torgb(lib, st, ref_raw, torch.eye(3, device=dev).reshape(1, 3, 3), None, rgb_bias, skip, k4)
-    for _ in range(3):
-        img = M.modconv3x3_f16_pre_image(lib, st, act, hi, lo, 3, dm, nz, nw, bias, (rgb_w, rgb_s), rgb_bias, skip, k4)
-        assert lib.hf_debug_last_path() == 579
-        torch.cuda.synchronize()
-        assert torch.equal(img, want_img)
-    if B * H * W <= 1 << 20:
-        exact = M.modconv3x3(lib, st, x, wt, s, dm, nz, nw, bias)
-        assert float((out - exact).abs().max()) <= 2e-5 * max(1.0, float(exact.abs().max()))
+@pytest.mark.parametrize("case", K.params("conv_rows", gpu=True))
+def test_conv_rows_pipeline_equals_tiled_kernel_on_hardware(case):
+    K.check_conv_rows(*_native(), case)
 
 
 def test_generator1024_block_order_does_not_change_the_image():
@@ -993,15 +652,11 @@ def test_small_plane_upsampling_in_two_launches_equals_three(B, h, monkeypatch):
     from hairfastgan_amd import _marshal as M
     from hairfastgan_amd._runtime import lib, stream
 
-    dev = torch.device("cuda:0")
+    dev = _dev()
     L, st = lib(), stream()
-    torch.manual_seed(h)
-    c = 512
-    k4 = O.blur_kernel_1d_to_2d(gain=4.0).to(dev)
-    x, wgt = torch.randn(B, c, h, h, device=dev), torch.randn(1, c, c, 3, 3, device=dev)
-    s, d, s2 = (torch.rand(B, c, device=dev) + 0.5 for _ in range(3))
-    nz, nw, bias = torch.randn(B, 1, 2 * h, 2 * h, device=dev), torch.tensor([0.3], device=dev), torch.randn(c, device=dev)
-    wt, _ = M.prepare_weights(L, st, wgt)
+    lay = K.styled_layer(L, st, dev, (B, 512, 512, h, h), h, True)
+    x, wt, s, d, k4, nz, nw, bias = lay.x, lay.wt, lay.s, lay.dm, lay.k4, lay.nz, lay.nw, lay.bias
+    s2 = (torch.rand(B, 512) + 0.5).to(dev)
     w9 = M.split_weights_small(L, st, wt)
     for split_for in (None, (None, s2, True)):
         res = {}
@@ -1023,14 +678,11 @@ def test_small_plane_tap_gemm_pixel_tile_forms_agree(B):
     from hairfastgan_amd import _marshal as M
     from hairfastgan_amd._runtime import lib, stream
 
-    dev = torch.device("cuda:0")
+    dev = _dev()
     L, st = lib(), stream()
-    torch.manual_seed(B)
     c, h = 512, 16
-    x, wgt = torch.randn(B, c, h, h, device=dev), torch.randn(1, c, c, 3, 3, device=dev)
-    s, d = torch.rand(B, c, device=dev) + 0.5, torch.rand(B, c, device=dev) + 0.5
-    nz, nw, bias = torch.randn(B, 1, h, h, device=dev), torch.tensor([0.3], device=dev), torch.randn(c, device=dev)
-    wt, _ = M.prepare_weights(L, st, wgt)
+    lay = K.styled_layer(L, st, dev, (B, c, c, h, h), B, False)
+    x, wt, s, d, nz, nw, bias = lay.x, lay.wt, lay.s, lay.dm, lay.nz, lay.nw, lay.bias
     w9 = M.split_weights_small(L, st, wt)
     same, up = {}, {}
     try:

@@ -9,7 +9,7 @@ of the whole output."""
 import torch
 
 from hairfastgan_amd import _marshal as M
-from oracle import ref_stylegan2 as O
+from tests.conv_kernel_checks import oracle, presplit, styled_layer
 
 RIM_FAMILIES = 32  # hf_debug_set_tuning bit 5
 
@@ -25,19 +25,11 @@ CASES = [
 
 def check_case(lib, st, dev, shape, nterms, with_split=True):
     B, cin, cout, H, W = shape
-    torch.manual_seed(11)
-    x = torch.randn(B, cin, H, W, device=dev)
-    wgt = torch.randn(1, cout, cin, 3, 3, device=dev)
-    mw, mb, sty = torch.randn(cin, 16, device=dev), torch.randn(cin, device=dev), torch.randn(B, 16, device=dev)
-    nz, nw, bias = torch.randn(B, 1, 2 * H, 2 * W, device=dev), torch.tensor([0.3], device=dev), torch.randn(cout, device=dev)
-    s_next = torch.rand(B, cout, device=dev) + 1.0
-    wt, wsq = M.prepare_weights(lib, st, wgt)
-    s = M.modulation(lib, st, sty, mw, mb)
-    dm = M.demod(lib, st, s, wsq)
-    hi, lo = M.split_weights_f16(lib, st, wt)
-    k4 = O.blur_kernel_1d_to_2d(gain=4.0).to(dev)
+    L = styled_layer(lib, st, dev, shape, 11, True)
+    s_next = (torch.rand(B, cout) + 1.0).to(dev)
+    wt, dm, hi, lo, k4, nz, nw, bias = L.wt, L.dm, L.hi, L.lo, L.k4, L.nz, L.nw, L.bias
     assert M.modconv3x3_up_f16_supported(cin, cout, H, W)
-    act = M.SplitActivation(*M.split_activation_reference(x, s), None)
+    act = presplit(L)
     want_path = 583 if cout % 64 else 581
     res = {}
     try:
@@ -63,8 +55,7 @@ def check_case(lib, st, dev, shape, nterms, with_split=True):
         if nterms == 3:
             assert torch.equal(sp.lo, sp_old.lo)
     if cin <= 64:
-        full = O.fused_leaky_relu(O.modulated_conv2d(x.cpu(), sty.cpu(), wgt.cpu(), mw.cpu(), mb.cpu(), True, True)
-                                  + nw.cpu() * nz.cpu(), bias.cpu())
+        full = oracle(L)
         scale = max(1.0, float(full.abs().max()))
         err = float((y.cpu() - full).abs().max())
         print(f"up_rim {shape} nterms {nterms}: max-abs vs oracle {err:.3e} (bound {(1e-5 if nterms == 3 else 4e-3) * scale:.3e})")
