@@ -452,8 +452,9 @@ __device__ __forceinline__ void store_tile_rows(const ConvParams &P, const TileG
 // LDS carve-up of the fp16 3x3 kernels (conv_mfma_h, conv_enc_h, conv_enc_s2mt_h) in 16-byte units, for the kernel to carve
 // and its launcher to allocate: two stage buffers [W hi][W lo][X hi][X lo] (lo: f16x3 only), then the kernel's fp32 tables.
 // MIN_UNITS: a stage buffer that doubles as something larger (conv_mfma_h FUSE: the epilogue's vertical exchange).
-template <int NTERMS, int CT, int NPIX_, int MIN_UNITS = 0>
+template <int NTERMS, int CT_, int NPIX_, int MIN_UNITS = 0>
 struct StageLayout {
+  static constexpr int CT = CT_;  // output channels of the block
   static constexpr int NPIX = NPIX_;
   static constexpr int NPART = (NTERMS == 3) ? 2 : 1;  // hi (+ lo)
   static constexpr int W_UNITS = 9 * 2 * CT;           // 16-byte units of one weight part per stage
@@ -464,6 +465,81 @@ struct StageLayout {
   // floats of the [2][cin] per-input-channel table behind the stages (rows padded to 16 bytes)
   __host__ __device__ static constexpr int cin_table_floats(int cin) { return 2 * ((cin + 3) & ~3); }
 };
+
+// ---- kernel-side text of the fp16 convolutions stated once ---------------------------------------------
+
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));  // one MFMA operand fragment = one 16-byte LDS unit
+constexpr int KH = 16;  // input channels per K step = K of one v_mfma_f32_32x32x16_f16
+
+// One K step of 16 input channels into a set of CT_TILES x PG accumulator tiles, acc[ct * PG + g] (a pointer to the first
+// tile: acc[ph][0] of conv_mfma_h's [NPH][CT_TILES][PG]), from the A fragments ah / al [CT_TILES] (weights, hi / lo) and the
+// B fragments bh / bl [PG] (activations, hi / lo), all given as pointers: hi*hi for every (ct, g), then - NTERMS 3, the f16x3
+// operand mode - hi*lo for every pair, then lo*hi; al / bl are not evaluated with NTERMS 1.
+// Every accumulator therefore receives hh -> hl -> lh, K steps ascending: THAT order fixes the bits of every fp16-core
+// kernel (the products are exact in fp32, the additions are not associative), so a change of the operand mode - dropping a
+// term, adding lo*lo - is made here.  The order ACROSS accumulators only decides how far apart dependent MFMAs issue.
+// The text is a macro, like HF_STD_STYLED_TAIL below; mfma_f16x3 wraps it as a function and is what a kernel calls.  Three sites
+// paste the macro instead, because through the inlined function - fragments by pointer or as array references alike - hipcc
+// compiles them differently (tools/compare_isa.sh): conv_mfma_h (commutative operands swapped in the epilogues of 32 kernels),
+// the one-phase K loop of conv_enc_h (a loop test inverted in six kernels) and gemm1x1_h (its lo fragment is read where the
+// hi*lo MFMA stands, which only an argument expression can say).  conv_enc_s2mt_h is the reverse case: the function, not the macro.
+#define HF_MFMA_F16X3(NTERMS_, CT_TILES_, PG_, acc_, ah_, al_, bh_, bl_)                                                            \
+  {                                                                                                                               \
+    _Pragma("unroll") for (int ct_ = 0; ct_ < (CT_TILES_); ++ct_)                                                                 \
+      _Pragma("unroll") for (int g_ = 0; g_ < (PG_); ++g_)                                                                        \
+        (acc_)[ct_ * (PG_) + g_] =                                                                                                \
+            __builtin_amdgcn_mfma_f32_32x32x16_f16((ah_)[ct_], (bh_)[g_], (acc_)[ct_ * (PG_) + g_], 0, 0, 0);                     \
+    if constexpr ((NTERMS_) == 3) {                                                                                               \
+      _Pragma("unroll") for (int ct_ = 0; ct_ < (CT_TILES_); ++ct_)                                                               \
+        _Pragma("unroll") for (int g_ = 0; g_ < (PG_); ++g_)                                                                      \
+          (acc_)[ct_ * (PG_) + g_] =                                                                                              \
+              __builtin_amdgcn_mfma_f32_32x32x16_f16((ah_)[ct_], (bl_)[g_], (acc_)[ct_ * (PG_) + g_], 0, 0, 0);                   \
+      _Pragma("unroll") for (int ct_ = 0; ct_ < (CT_TILES_); ++ct_)                                                               \
+        _Pragma("unroll") for (int g_ = 0; g_ < (PG_); ++g_)                                                                      \
+          (acc_)[ct_ * (PG_) + g_] =                                                                                              \
+              __builtin_amdgcn_mfma_f32_32x32x16_f16((al_)[ct_], (bh_)[g_], (acc_)[ct_ * (PG_) + g_], 0, 0, 0);                   \
+    }                                                                                                                             \
+  }
+
+template <int NTERMS, int CT_TILES, int PG>
+__device__ __forceinline__ void mfma_f16x3(f32x16 *acc, const half8 *ah, const half8 *al, const half8 *bh, const half8 *bl) {
+  HF_MFMA_F16X3(NTERMS, CT_TILES, PG, acc, ah, al, bh, bl)
+}
+
+// Scheduling pattern of one tap-step of the ping-pong K loops (conv_mfma_h, conv_enc_h): NR times (one MFMA, one LDS read),
+// then the remaining MFMAs.  The LDS fragment reads of the NEXT tap are issued between the MFMAs of the current one instead
+// of in front of them - in its turn on the pipe a wave is alone on its SIMD, nothing else covers the ~150 cycles the eight
+// ds_read_b128 take to issue (profiles/r06af_trace_same_res_64ch.txt: step -> mfma 200 ticks per tap beside 500 of MFMAs)
+template <int NR, int NM>
+__device__ __forceinline__ void hf_interleave() {
+#pragma unroll
+  for (int k = 0; k < NR; ++k) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
+    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
+  }
+  if constexpr (NM > NR) __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
+}
+
+// Weights of K stage `chunk` into stage buffer `bufsel` (StageLayout L) by LDS-DMA, 64 units (1 KiB) per piece and wave: piece
+// wave + i * NW of the stage's NPART * W_UNITS / 64.  Uniform base (the chunk of the part's tensor) + per-lane byte offset
+// ((tap*2+kg)*cout + co0 + col)*16.  lds_addr0 = hf_lds_addr of the stage buffers (the address stays this sum of lds_addr0
+// and the unit expression: handed in pre-added per buffer, hipcc allocates registers differently - tools/compare_isa.sh).
+// WAVE_TEST: conv_mfma_h's form, see there.
+template <class L, int NW, bool WAVE_TEST = false>
+__device__ __forceinline__ void dma_weight_piece(int i, int chunk, int bufsel, int wave, int lane, const _Float16 *wth,
+                                                 const _Float16 *wtl, int cout, int co0, unsigned lds_addr0) {
+  constexpr int N_WPIECE = L::NPART * L::W_UNITS / 64;
+  const int pc = wave + i * NW;
+  if ((!WAVE_TEST || wave < NW) && pc < N_WPIECE) {
+    const int part = pc / (L::W_UNITS / 64), q = pc % (L::W_UNITS / 64);
+    const int u = q * 64 + lane;                  // unit inside the part: (tap*2 + kg)*CT + co
+    const int row = u / L::CT, col = u % L::CT;   // row = tap*2 + kg
+    int off = (row * cout + co0 + col) * 16;
+    HF_OPAQUE_I32(off);
+    const _Float16 *src = (part ? wtl : wth) + (long long)chunk * 18 * cout * 8;
+    hf_glds16_raw_s(src, (unsigned)off, lds_addr0 + (unsigned)(bufsel * L::BUF_UNITS + part * L::W_UNITS + q * 64) * 16u);
+  }
+}
 
 // The generator's standard StyledConv tail - noise + bias + leaky ReLU with 0 <= alpha <= 1, * scale > 0: conv_mfma_h's
 // straight-line epilogue (fast_ep), which is also the one that writes a fused ToRGB in several slabs (launch_h).

@@ -54,23 +54,6 @@ extern "C" int hf_debug_read_trace(unsigned long long *host, int n) {
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-constexpr int KH = 16;  // input channels per stage = K of one MFMA
-
-// Scheduling pattern of one tap-step of the ping-pong K loop: NR times (one MFMA, one LDS read), then the remaining MFMAs.
-// The LDS fragment reads of the NEXT tap are issued between the MFMAs of the current one instead of in front of them - in its
-// turn on the pipe a wave is alone on its SIMD, nothing else covers the ~150 cycles the eight ds_read_b128 take to issue
-// (profiles/r06af_trace_same_res_64ch.txt: step -> mfma 200 ticks per tap beside 500 of MFMAs)
-template <int NR, int NM>
-__device__ __forceinline__ void hf_interleave() {
-#pragma unroll
-  for (int k = 0; k < NR; ++k) {
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
-    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
-  }
-  if constexpr (NM > NR) __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
-}
-
 // Halo pixels the LDS activation tile is sized for: PT-pixel tiles of 32..TWMAX-pixel rows, and
 // (UP) the 2-row / 2-column rim tiles of make_geom(one_image).  Wide tiles (TWMAX 128) turn the
 // 128-byte row segments of a 32-pixel-wide tile into 512-byte ones: the high-resolution layers
@@ -295,20 +278,14 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
   // weight stage of `chunk`: uniform base + per-lane byte offset ((tap*2+kg)*cout + co0 + col)*16
   const unsigned lds_addr0 = hf_lds_addr(lds);
   auto dma_piece = [&](int i, int chunk, int bufsel) {
-    const int pc = wave + i * NW;
-    if (wave < NW && pc < N_WPIECE) {  // (wave < NW always holds, but hipcc allocates registers differently without it)
-      const int part = pc / (W_UNITS / 64), q = pc % (W_UNITS / 64);
-      const int u = q * 64 + lane;            // unit inside the part: (tap*2 + kg)*CT + co
-      const int row = u / CT, col = u % CT;   // row = tap*2 + kg
-      int off = (row * P.cout + co0 + col) * 16;
-      HF_OPAQUE_I32(off);
-      const _Float16 *src = (part ? wtl : wth) + (long long)chunk * 18 * P.cout * 8;
-      hf_glds16_raw_s(src, (unsigned)off, lds_addr0 + (unsigned)(bufsel * BUF_UNITS + part * W_UNITS + q * 64) * 16u);
-    }
+    // (WAVE_TEST: `wave < NW` always holds, but hipcc allocates registers differently without the test)
+    dma_weight_piece<L, NW, true>(i, chunk, bufsel, wave, lane, wth, wtl, P.cout, co0, lds_addr0);
   };
 
   // PRE: one (halo pixel, kgroup) unit per lane and item straight into LDS; halo pixels outside
   // the image are masked out of the DMA and zero-filled by the same lane
+  // (conv_enc_h and conv_enc_s2mt_h carry the same copy in their own text: shared as a function, every spelling tried made
+  // hipcc compile the kernels that use it differently - DESIGN 4.20)
   const char *xh_b = nullptr, *xl_b = nullptr;  // image base of the pre-split tensors (uniform)
   auto dma_x = [&](int e, int chunk, int bufsel) {
     const int i = tid + e * NT;
@@ -965,23 +942,7 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX, (WAVES_CO * WAVES_PX >= 1
         if (!ILV) __builtin_amdgcn_sched_barrier(0);
         HF_TRACE_POINT(20 + i);  // side work issued, before the MFMAs
         const int ph = UP ? (((tap / 3) & 1) * 2 + ((tap % 3) & 1)) : 0;
-#pragma unroll
-        for (int ct = 0; ct < CT_TILES; ++ct)
-#pragma unroll
-          for (int g = 0; g < PG; ++g)
-            acc[ph][ct][g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sa][ct], bh[sb][g], acc[ph][ct][g], 0, 0, 0);
-        if (NTERMS == 3) {
-#pragma unroll
-          for (int ct = 0; ct < CT_TILES; ++ct)
-#pragma unroll
-            for (int g = 0; g < PG; ++g)
-              acc[ph][ct][g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sa][ct], bl[sb][g], acc[ph][ct][g], 0, 0, 0);
-#pragma unroll
-          for (int ct = 0; ct < CT_TILES; ++ct)
-#pragma unroll
-            for (int g = 0; g < PG; ++g)
-              acc[ph][ct][g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[sa][ct], bh[sb][g], acc[ph][ct][g], 0, 0, 0);
-        }
+        HF_MFMA_F16X3(NTERMS, CT_TILES, PG, acc[ph][0], ah[sa], al[sa], bh[sb], bl[sb]);
         if constexpr (ILV) {
           constexpr int NRA = CT_TILES * (NTERMS == 3 ? 2 : 1), NRB = PG * (NTERMS == 3 ? 2 : 1), NM = CT_TILES * PG * NTERMS;
           const bool fb = group_first<UP>(grp) == i && group_first<UP>(grp + 1) < 9;  // this step fetched the next group's B fragments
@@ -1158,11 +1119,7 @@ __global__ __launch_bounds__(64) void conv_up_rim_h(const ConvParams P, const _F
     half8 bv[NPART];
 #pragma unroll
     for (int part = 0; part < NPART; ++part) bv[part] = ok ? bf[part] : zero;
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], bv[0], acc, 0, 0, 0);
-    if constexpr (NTERMS == 3) {
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], bv[NPART - 1], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[NPART - 1], bv[0], acc, 0, 0, 0);
-    }
+    mfma_f16x3<NTERMS, 1, 1>(&acc, &a[0], &a[NPART - 1], &bv[0], &bv[NPART - 1]);
   };
 
   // chunk c sits in slot c % RIM_DEPTH; its slot is refilled with chunk c + RIM_DEPTH right after its MFMAs (past the last

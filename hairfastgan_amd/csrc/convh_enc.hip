@@ -35,21 +35,6 @@ using namespace hf_detail;
 
 namespace {
 
-// Scheduling pattern of one tap-step of the ping-pong K loop (the next tap's LDS fragment reads issued between the current
-// tap's MFMAs): NR times (one MFMA, one LDS read), then the remaining MFMAs
-template <int NR, int NM>
-__device__ __forceinline__ void hf_enc_interleave() {
-#pragma unroll
-  for (int k = 0; k < NR; ++k) {
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
-    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
-  }
-  if constexpr (NM > NR) __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
-}
-
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-constexpr int KH = 16;  // input channels per stage = K of one MFMA
 constexpr int S2MT_MAX = 4;  // pixel tiles per resident weight stage of the stride-2 multi-tile form (at most)
 
 #ifdef HF_ENC_TRACE
@@ -94,6 +79,24 @@ struct EncLayout : StageLayout<NTERMS, 64, enc_npix<PT, STRIDE>()> {
 // the block's own epilogue finishes the tile: the bits of the two-launch form without its slabs and its second launch.
 template <int NTERMS, int CT_TILES, bool VSPLIT>
 __host__ __device__ constexpr bool enc_persist_ok() { return !(VSPLIT && CT_TILES == 2 && NTERMS == 3); }
+
+// conv_enc_h: the fragments of `tap` of the stage whose bases a_hi / b_hi the caller holds, into register slot `slot` - used
+// by both K-loop forms.  (The lambda's text as a macro: as ONE lambda ahead of the loops - the bases as parameters, the stage
+// buffer as a parameter, or captured variables set per stage - hipcc compiles up to 24 of the 30 kernels differently,
+// tools/compare_isa.sh.)
+#define HF_ENC_FETCH                                                                                      \
+  [&](int slot, int tap) {                                                                                \
+    const int ky = tap / 3, kx = tap % 3;                                                                 \
+    const int toff = (STRIDE == 1) ? ky * wp + kx : ky * wp + (kx & 1) * wp2 + (kx >> 1);                 \
+    _Pragma("unroll") for (int ct = 0; ct < CT_TILES; ++ct) {                                             \
+      ah[slot][ct] = a_hi[tap * 2 * CT + ct * 32];                                                        \
+      if (NTERMS == 3) al[slot][ct] = a_hi[OFF_WL + tap * 2 * CT + ct * 32];                              \
+    }                                                                                                     \
+    _Pragma("unroll") for (int g = 0; g < PG; ++g) {                                                      \
+      bh[slot][g] = b_hi[pix0[g] + toff];                                                                 \
+      if (NTERMS == 3) bl[slot][g] = b_hi[X_UNITS + pix0[g] + toff];                                      \
+    }                                                                                                     \
+  }
 
 template <int NTERMS, int PG, int WAVES_PX, int STRIDE, bool PRE, int CT_TILES = 1, int WAVES_CO = 2, bool VSPLIT = false>
 __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX) void conv_enc_h(const ConvParams P, const _Float16 *__restrict__ wth_all,
@@ -171,25 +174,16 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX) void conv_enc_h(const Con
 
   const unsigned lds_addr0 = hf_lds_addr(lds);
   auto dma_piece = [&](int i, int chunk, int bufsel) {
-    const int pc = wave + i * NW;
-    if (pc < N_WPIECE) {
-      const int part = pc / (W_UNITS / 64), q = pc % (W_UNITS / 64);
-      const int u = q * 64 + lane;           // unit inside the part: (tap*2 + kg)*CT + co
-      const int row = u / CT, col = u % CT;  // row = tap*2 + kg
-      int off = (row * P.cout + co0 + col) * 16;
-      HF_OPAQUE_I32(off);
-      const _Float16 *src = (part ? wtl : wth) + (long long)chunk * 18 * P.cout * 8;
-      hf_glds16_raw_s(src, (unsigned)off, lds_addr0 + (unsigned)(bufsel * BUF_UNITS + part * W_UNITS + q * 64) * 16u);
-    }
+    dma_weight_piece<L, NW>(i, chunk, bufsel, wave, lane, wth, wtl, P.cout, co0, lds_addr0);
   };
-  // Fast prologue (round 5; tools/probes/trace_enc_layer.py: index arithmetic 2.4-3.3 k cycles, zero fill 1-1.5 k, first
-  // stage 3-7.7 k - together 1.3 K stages per block, whatever the layer): the first stage's weights leave at once (they depend on
-  // nothing below), its activations as soon as their addresses exist; only the halo units OUTSIDE the image are zeroed (by the
-  // lanes that own them; the masked DMA never writes them) instead of both activation regions, and the divisions by the halo
-  // pitch are divisions by its two possible values.
+  // Prologue with pre-split input (round 5; tools/probes/trace_enc_layer.py: index arithmetic 2.4-3.3 k cycles, zero fill
+  // 1-1.5 k, first stage 3-7.7 k - together 1.3 K stages per block, whatever the layer): the first stage's weights leave at once
+  // (they depend on nothing below), its activations as soon as their addresses exist; only the halo units OUTSIDE the image are
+  // zeroed (by the lanes that own them; the masked DMA never writes them) instead of both activation regions, and the divisions
+  // by the halo pitch are divisions by its two possible values.
+  // (c_first = c_begin below, stated a second time: with c_begin itself moved up here the register-staged kernels compile differently)
   const int c_first = (P.splits > 1 && !VSPLIT) ? (int)blockIdx.z * P.chunks_per_split : 0;
-  constexpr bool FASTP = PRE;
-  if (FASTP) {
+  if (PRE) {
 #pragma unroll
     for (int i = 0; i < ND; ++i) dma_piece(i, c_first, 0);
   }
@@ -306,7 +300,7 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX) void conv_enc_h(const Con
         for (int r = 0; r < 16; ++r) vsum[VSPLIT ? ct : 0][VSPLIT ? g : 0][r] = 0.0f;
   }
   HF_ENC_TRACE_POINT(1);  // index arithmetic done
-  if (FASTP) {
+  if (PRE) {
 #pragma unroll
     for (int e = 0; e < XE; ++e) dma_x(e, c_begin, 0);
     half8 z;
@@ -322,26 +316,13 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX) void conv_enc_h(const Con
           lds[BUF_UNITS + OFF_XL + e_dst[e]] = z;
         }
       }
-  } else if (PRE) {  // zero the activation regions of both buffers once: DMA-masked units (padding) stay zero
-    half8 z;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) z[k] = (_Float16)0.0f;
-    for (int i = tid; i < NPART * X_UNITS; i += NT) {
-      lds[OFF_XH + i] = z;
-      lds[BUF_UNITS + OFF_XH + i] = z;
-    }
+  } else {
+    __syncthreads();  // sl / tl visible
   }
-  if (!FASTP) __syncthreads();  // sl / tl (or the zero fill) visible
   HF_ENC_TRACE_POINT(2);  // LDS zero fill done
-  if (!FASTP) {
+  if (!PRE) {
 #pragma unroll
     for (int i = 0; i < ND; ++i) dma_piece(i, c_begin, 0);
-  }
-  if (FASTP) {
-  } else if (PRE) {
-#pragma unroll
-    for (int e = 0; e < XE; ++e) dma_x(e, c_begin, 0);
-  } else {
 #pragma unroll
     for (int e = 0; e < XE; ++e) load_item(e, c_begin);
 #pragma unroll
@@ -363,46 +344,17 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX) void conv_enc_h(const Con
   auto compute_stage = [&](const half8 *buf) {  // the 9 taps of one K stage: fragments of tap+1 fetched under the MFMAs of tap
     const half8 *a_hi = buf + lh * CT + wave_co + li;  // + tap*2*CT
     const half8 *b_hi = buf + OFF_XH + lh * NPIX;
-    auto fetch = [&](int slot, int tap) {
-      const int ky = tap / 3, kx = tap % 3;
-      const int toff = (STRIDE == 1) ? ky * wp + kx : ky * wp + (kx & 1) * wp2 + (kx >> 1);
-#pragma unroll
-      for (int ct = 0; ct < CT_TILES; ++ct) {
-        ah[slot][ct] = a_hi[tap * 2 * CT + ct * 32];
-        if (NTERMS == 3) al[slot][ct] = a_hi[OFF_WL + tap * 2 * CT + ct * 32];
-      }
-#pragma unroll
-      for (int g = 0; g < PG; ++g) {
-        bh[slot][g] = b_hi[pix0[g] + toff];
-        if (NTERMS == 3) bl[slot][g] = b_hi[X_UNITS + pix0[g] + toff];
-      }
-    };
+    auto fetch = HF_ENC_FETCH;
     fetch(0, 0);
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
       const int s_ = tap & 1;
       if (tap + 1 < 9) fetch(s_ ^ 1, tap + 1);
-#pragma unroll
-      for (int ct = 0; ct < CT_TILES; ++ct)
-#pragma unroll
-        for (int g = 0; g < PG; ++g)
-          acc[0][ct][g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s_][ct], bh[s_][g], acc[0][ct][g], 0, 0, 0);
-      if (NTERMS == 3) {
-#pragma unroll
-        for (int ct = 0; ct < CT_TILES; ++ct)
-#pragma unroll
-          for (int g = 0; g < PG; ++g)
-            acc[0][ct][g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s_][ct], bl[s_][g], acc[0][ct][g], 0, 0, 0);
-#pragma unroll
-        for (int ct = 0; ct < CT_TILES; ++ct)
-#pragma unroll
-          for (int g = 0; g < PG; ++g)
-            acc[0][ct][g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[s_][ct], bh[s_][g], acc[0][ct][g], 0, 0, 0);
-      }
+      mfma_f16x3<NTERMS, CT_TILES, PG>(acc[0][0], ah[s_], al[s_], bh[s_], bl[s_]);
       // (round 6) the next tap's fragment reads BETWEEN this tap's MFMAs, one behind each: in its turn on the pipe the wave is
-      // alone on its SIMD - nothing else covers the time the reads take to issue (see hf_interleave, csrc/convh.hip)
+      // alone on its SIMD - nothing else covers the time the reads take to issue (see hf_interleave, conv_common.h)
       constexpr int NRD = (CT_TILES + PG) * (NTERMS == 3 ? 2 : 1), NM = CT_TILES * PG * NTERMS;
-      if (tap + 1 < 9) hf_enc_interleave<(NRD < NM ? NRD : NM), NM>();
+      if (tap + 1 < 9) hf_interleave<(NRD < NM ? NRD : NM), NM>();
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -454,20 +406,7 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX) void conv_enc_h(const Con
     }
     const half8 *a_hi = buf + lh * CT + wave_co + li;  // + tap*2*CT
     const half8 *b_hi = buf + OFF_XH + lh * NPIX;
-    auto fetch = [&](int slot, int tap) {
-      const int ky = tap / 3, kx = tap % 3;
-      const int toff = (STRIDE == 1) ? ky * wp + kx : ky * wp + (kx & 1) * wp2 + (kx >> 1);
-#pragma unroll
-      for (int ct = 0; ct < CT_TILES; ++ct) {
-        ah[slot][ct] = a_hi[tap * 2 * CT + ct * 32];
-        if (NTERMS == 3) al[slot][ct] = a_hi[OFF_WL + tap * 2 * CT + ct * 32];
-      }
-#pragma unroll
-      for (int g = 0; g < PG; ++g) {
-        bh[slot][g] = b_hi[pix0[g] + toff];
-        if (NTERMS == 3) bl[slot][g] = b_hi[X_UNITS + pix0[g] + toff];
-      }
-    };
+    auto fetch = HF_ENC_FETCH;
     fetch(0, 0);
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
@@ -490,23 +429,7 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX) void conv_enc_h(const Con
         }
       }
       __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int ct = 0; ct < CT_TILES; ++ct)
-#pragma unroll
-        for (int g = 0; g < PG; ++g)
-          acc[0][ct][g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s_][ct], bh[s_][g], acc[0][ct][g], 0, 0, 0);
-      if (NTERMS == 3) {
-#pragma unroll
-        for (int ct = 0; ct < CT_TILES; ++ct)
-#pragma unroll
-          for (int g = 0; g < PG; ++g)
-            acc[0][ct][g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s_][ct], bl[s_][g], acc[0][ct][g], 0, 0, 0);
-#pragma unroll
-        for (int ct = 0; ct < CT_TILES; ++ct)
-#pragma unroll
-          for (int g = 0; g < PG; ++g)
-            acc[0][ct][g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[s_][ct], bh[s_][g], acc[0][ct][g], 0, 0, 0);
-      }
+      HF_MFMA_F16X3(NTERMS, CT_TILES, PG, acc[0][0], ah[s_], al[s_], bh[s_], bl[s_]);
       __builtin_amdgcn_sched_barrier(0);
     }
     slab_end(more);
@@ -539,6 +462,8 @@ __global__ __launch_bounds__(64 * WAVES_CO * WAVES_PX) void conv_enc_h(const Con
   if (persist) __syncthreads();  // every wave is done with the stage buffers (and sl / tl): the next tile's copies may land
   }
 }
+
+#undef HF_ENC_FETCH
 
 // ---- stride 2, several pixel tiles per resident weight stage (round 5) -------------------------------------------------------
 // A stride-2 conv reads four input pixels per output pixel: its 64 co x 128 px blocks move 36.9 KB of weights + 38 KB of
@@ -623,16 +548,7 @@ __global__ __launch_bounds__(512) void conv_enc_s2mt_h(const ConvParams P, const
 
   const unsigned lds_addr0 = hf_lds_addr(lds);
   auto dma_piece = [&](int i, int chunk, int wbuf) {
-    const int pc = wave + i * NW;
-    if (pc < N_WPIECE) {
-      const int part = pc / (W_UNITS / 64), q = pc % (W_UNITS / 64);
-      const int u = q * 64 + lane;
-      const int row = u / CT, col = u % CT;
-      int off = (row * P.cout + co0 + col) * 16;
-      HF_OPAQUE_I32(off);
-      const _Float16 *src = (part ? wtl : wth) + (long long)chunk * 18 * P.cout * 8;
-      hf_glds16_raw_s(src, (unsigned)off, lds_addr0 + (unsigned)(wbuf * BUF_UNITS + part * W_UNITS + q * 64) * 16u);
-    }
+    dma_weight_piece<L, NW>(i, chunk, wbuf, wave, lane, wth, wtl, P.cout, co0, lds_addr0);
   };
   // activations of (chunk, tile j) into the X region of buffer xbuf; halo units outside the image are written as zeros by
   // their lanes (the tiles of a block differ in which units those are: nothing can be zeroed once and for all)
@@ -726,11 +642,7 @@ __global__ __launch_bounds__(512) void conv_enc_s2mt_h(const ConvParams P, const
         const int ws = AREG ? tap : s_;
         if (tap + 1 < 9) fetch(s_ ^ 1, tap + 1);
         __builtin_amdgcn_sched_barrier(0);
-        acc[j][0][0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[ws], bh[s_], acc[j][0][0][0], 0, 0, 0);
-        if (NTERMS == 3) {
-          acc[j][0][0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[ws], bl[s_], acc[j][0][0][0], 0, 0, 0);
-          acc[j][0][0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[ws], bh[s_], acc[j][0][0][0], 0, 0, 0);
-        }
+        mfma_f16x3<NTERMS, 1, 1>(&acc[j][0][0][0], &wh[ws], &wl[ws], &bh[s_], &bl[s_]);
         __builtin_amdgcn_sched_barrier(0);
       }
       hf_barrier_keep_young<0>();  // next step's copies landed, this step's buffers free

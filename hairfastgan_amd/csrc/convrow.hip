@@ -28,8 +28,6 @@ using namespace hf_detail;
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
 constexpr int kSW = 64;                      // output columns of a strip
 constexpr int kPXW = kSW + 2;                // staged columns (x0 - 1 .. x0 + 64)
 constexpr int kPartUnits = 4 * kPXW;         // 16-byte units of one part (hi or lo) of a row slot: [channel block 4][66]
@@ -190,14 +188,7 @@ __global__ __launch_bounds__(512, 2) void conv_rows_h(const ConvParams P, const 
       if (i + 1 < 18) fetch(i + 1, sl ^ 1);
       if (dma && i < NPART * kDmaPerPart) dma_piece(i, y_next, slot_next);
       __builtin_amdgcn_sched_barrier(0);
-      acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[c][t], bh[sl][0], acc[0], 0, 0, 0);
-      acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[c][t], bh[sl][1], acc[1], 0, 0, 0);
-      if constexpr (NTERMS == 3) {
-        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[c][t], bl[sl][0], acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[c][t], bl[sl][1], acc[1], 0, 0, 0);
-        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[c][t], bh[sl][0], acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[c][t], bh[sl][1], acc[1], 0, 0, 0);
-      }
+      mfma_f16x3<NTERMS, 1, 2>(acc, &ah[c][t], &al[NTERMS == 3 ? c : 0][NTERMS == 3 ? t : 0], bh[sl], bl[NTERMS == 3 ? sl : 0]);
       __builtin_amdgcn_sched_barrier(0);
     }
   };

@@ -23,8 +23,6 @@ using namespace hf_detail;
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-constexpr int KH = 16;   // input channels per MFMA k-step
 constexpr int KS = 32;   // input channels per LDS stage
 // Two blocks per CU: the 64 x 256 form's two stage buffers are exactly 80 KiB - half of a CU's 160 KiB - but without a register bound
 // hipcc spends 290 registers on it (one wave per SIMD, every LDS / DMA latency exposed); bounded to two waves per SIMD it needs
@@ -227,12 +225,7 @@ __global__ __launch_bounds__(128 * CW, 2) void gemm1x1_h(const ConvParams P, con
       for (int g = 0; g < PG; ++g) {
         const int u = (cs * 2 + lh) * PT + (wave_pg + g) * 32 + li;
         const half8 bh = buf[OFF_XH + u];
-        acc[0][0][g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[0][0][g], 0, 0, 0);
-        if (NTERMS == 3) {
-          const half8 bl = buf[OFF_XL + u];
-          acc[0][0][g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[0][0][g], 0, 0, 0);
-          acc[0][0][g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[0][0][g], 0, 0, 0);
-        }
+        HF_MFMA_F16X3(NTERMS, 1, 1, &acc[0][0][g], &ah, &al, &bh, &buf[OFF_XL + u]);  // (the lo fragment is read where its MFMA stands)
       }
     }
     if (more) convert_x(s + 1, nbuf);
@@ -472,7 +465,6 @@ __global__ __launch_bounds__(256) void small_combine(float *__restrict__ out, co
   }
 }
 
-typedef _Float16 hf_half8_g __attribute__((ext_vector_type(8)));
 extern "C" int hf_split_activation_mod_f16(void *out_hi, void *out_lo, const float *x, const float *scale, long long images,
                                            int channels, int h, int w, void *stream);
 
@@ -564,8 +556,8 @@ extern "C" int hf_modconv3x3_small_f16_f32(float *out, const float *x, const voi
 // become ~30 us.  Arithmetic = small_combine (up) followed by blur4x4_noise_bias_act / blur4x4_split8, operation for
 // operation: bit-identical to the three-launch path (tests/test_sim_generator.py, tests/test_gpu_parity.py).
 template <bool SPLIT>
-__global__ __launch_bounds__(1024) void small_up_blur(float *__restrict__ out, hf_half8_g *__restrict__ out_hi,
-                                                      hf_half8_g *__restrict__ out_lo, const float *__restrict__ y, int splits,
+__global__ __launch_bounds__(1024) void small_up_blur(float *__restrict__ out, half8 *__restrict__ out_hi,
+                                                      half8 *__restrict__ out_lo, const float *__restrict__ y, int splits,
                                                       long long zslab, const float *__restrict__ d,
                                                       const float *__restrict__ kernel4x4, const float *__restrict__ noise,
                                                       const float *__restrict__ noise_w, long long noise_bstride,
@@ -682,7 +674,7 @@ __global__ __launch_bounds__(1024) void small_up_blur(float *__restrict__ out, h
 #pragma unroll
       for (int c = 0; c < 8; ++c) out[(((long long)b * cout + cb * 8 + c) * out_h + oy) * out_w + ox] = res[c];
     } else {
-      hf_half8_g h8, l8;
+      half8 h8, l8;
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
         float v = res[c] * (s_next ? s_next[(long long)b * cout + cb * 8 + c] : 1.0f);
@@ -717,8 +709,8 @@ extern "C" int hf_modconv3x3_small_up_blur_f16_f32(float *out, void *out_hi, voi
   const int splits = P.vsplit ? 1 : P.splits;
   const dim3 grid(batch * (cout >> 3));
   if (out_hi)
-    hipLaunchKernelGGL(small_up_blur<true>, grid, dim3(1024), lds, (hipStream_t)stream, nullptr, static_cast<hf_half8_g *>(out_hi),
-                       static_cast<hf_half8_g *>(out_lo), workspace, splits, P.zslab, d, blur_kernel4x4, noise, noise_w, noise_bstride,
+    hipLaunchKernelGGL(small_up_blur<true>, grid, dim3(1024), lds, (hipStream_t)stream, nullptr, static_cast<half8 *>(out_hi),
+                       static_cast<half8 *>(out_lo), workspace, splits, P.zslab, d, blur_kernel4x4, noise, noise_w, noise_bstride,
                        bias, s_next, cout, h, w, alpha, scale);
   else
     hipLaunchKernelGGL(small_up_blur<false>, grid, dim3(1024), lds, (hipStream_t)stream, out, nullptr, nullptr, workspace, splits,

@@ -23,8 +23,6 @@ using namespace hf_detail;
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
 constexpr int kStemGroups = 22;   // K groups of 8: (ci, ky) = group / 7, group % 7 for the first 21; the last is zero
 constexpr int kStemSteps = 11;    // MFMA K-steps of 16
 constexpr int kStemPitch = 72;    // halves per window row: 2*31 + 7 = 69 used, + the zero-weight eighth tap
@@ -140,9 +138,7 @@ __global__ __launch_bounds__(256, 2) void stem7x7s2(float *__restrict__ out, con
         }
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) {
-          acc[g][ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ct], bh.h, acc[g][ct], 0, 0, 0);
-          acc[g][ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ct], bl.h, acc[g][ct], 0, 0, 0);
-          acc[g][ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[ct], bh.h, acc[g][ct], 0, 0, 0);
+          mfma_f16x3<3, 1, 1>(&acc[g][ct], &ah[ct], &al[ct], &bh.h, &bl.h);
         }
       }
       __builtin_amdgcn_sched_barrier(0);  // one K-step's fragments live at a time (unbounded, the scheduler hoists them all and spills)
