@@ -79,6 +79,7 @@ SIGNATURES = {
     "hf_multiply_u8": [_f, _f, _f, _ll, _st],
     "hf_image_to_bytes_f32": [_f, _f, _i, _i, _i, _fl, _fl, _i, _i, _st],
     "hf_labels_to_rgb_i64": [_f, _f, _ll, _f, _i, _i, _st],
+    "hf_png_encode_u8": [_f, _ll, _f, _f, _i, _i, _i, _i, _i, _f, _ll, _st],
     "hf_maxpool3x3s2_f32": [_f, _f, _ll, _i, _i, _st],
     "hf_gate_f32": [_f, _f, _f, _f, _f, _fl, _ll, _i, _st],
     "hf_upsample_nearest_f32": [_f, _f, _ll, _i, _i, _i, _i, _st],
@@ -119,6 +120,9 @@ SIGNATURES = {
     "hf_conv1x1_f16_workspace_floats": (_ll, [_i, _i, _i, _i, _i, _i, _i]),
     "hf_sample_layernorm_workspace_floats": (_ll, [_i, _i, _i]),
     "hf_f16_overflow_count": (_ll, [_i]),
+    "hf_png_bound": (_ll, [_i, _i, _i]),
+    "hf_png_segment_rows": [_i, _i, _i],
+    "hf_png_workspace_bytes": (_ll, [_i, _i, _i, _i]),
 }
 
 

@@ -1476,3 +1476,30 @@ def labels_to_rgb(lib, st, labels, palette, unknown_label=255):
     check(lib, lib.hf_labels_to_rgb_i64(_p(out), _p(labels), labels.numel(), _p(palette), palette.shape[0], int(unknown_label), st),
           "hf_labels_to_rgb_i64")
     return out
+
+
+PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "adaptive": 3}
+
+
+def png_encode(lib, st, images, filter_mode=3):
+    """uint8 [B,H,W,C] (C = 1 or 3, interleaved) -> (files uint8 [B,stride], sizes int64 [B]) on the images' device: image b's
+    PNG file is files[b, :sizes[b]] (csrc/png.h).  Nothing is synchronised; stride >= hf_png_bound."""
+    if images.dtype != torch.uint8:
+        raise TypeError(f"expected uint8 images; got {images.dtype}")
+    if images.ndim != 4 or images.shape[3] not in (1, 3) or images.numel() == 0:
+        raise ValueError(f"expected images [B,H,W,1] or [B,H,W,3] with B, H, W > 0; got {tuple(images.shape)}")
+    if filter_mode not in (0, 1, 2, 3):
+        raise ValueError(f"filter mode must be 0..3; got {filter_mode}")
+    images = images if images.is_contiguous() else images.contiguous()
+    b, h, w, c = images.shape
+    bound = lib.hf_png_bound(h, w, c)
+    if bound <= 0:
+        raise ValueError(f"hf_png_encode_u8 does not take images of {h}x{w}x{c}: a row of at most 24639 bytes, a file below 2 GiB")
+    stride = (bound + 15) // 16 * 16
+    ws_bytes = lib.hf_png_workspace_bytes(b, h, w, c)
+    files = torch.empty((b, stride), dtype=torch.uint8, device=images.device)
+    sizes = torch.empty((b,), dtype=torch.int64, device=images.device)
+    ws = torch.empty((ws_bytes + 15) // 16 * 2, dtype=torch.int64, device=images.device)
+    check(lib, lib.hf_png_encode_u8(_p(files), stride, _p(sizes), _p(images), b, h, w, c, int(filter_mode), _p(ws), ws.numel() * 8, st),
+          "hf_png_encode_u8")
+    return files, sizes

@@ -63,6 +63,8 @@ def get_parser():
     parser.add_argument("--device", type=str, default="cuda")
     parser.add_argument("--batch_size", type=int, default=3, help="batch size for encoding images")
     parser.add_argument("--save_all", action="store_true")
+    parser.add_argument("--png_encoder", choices=("pil", "device"), default="pil",
+                        help="who makes the PNG files of --save_all: PIL (zlib on the host) or the GPU (image_utils.encode_png)")
     parser.add_argument("--mixing", type=float, default=0.95)
     parser.add_argument("--smooth", type=int, default=5)
     parser.add_argument("--rotate_checkpoint", type=str, default="pretrained_models/Rotate/rotate_best.pth")
@@ -723,11 +725,18 @@ class SaveAllRecorder:
     * `write` copies bytes and latents to the host and writes the reference's layout under
       save_all_dir / exp_name: W+/ FS/ Shape/ Align/ Blending/ Final/ with its file names (PIL, np.savez).
 
+    `png_encoder="device"`: `render` also enqueues one PNG encode per quantised batch and per coloured parse tensor
+    (hf_png_encode_u8, no synchronisation), and `write` copies only the encoded files and writes them as they are: no pixel
+    reaches the host.  The files decode to the same pixels as PIL's; "pil" (the default) runs none of this.
+
     Deviation from the reference, on purpose: Embedding.py:94 rebinds `names` in its loop, so its W+/ and FS/ files pair the
     last image's names with the first images' tensors; here every image is written under every one of its own names."""
 
-    def __init__(self, root):
+    def __init__(self, root, png_encoder="pil"):
+        if png_encoder not in ("pil", "device"):
+            raise ValueError(f"png_encoder must be 'pil' or 'device'; got {png_encoder!r}")
         self.root = Path(root)
+        self.png_encoder = png_encoder
         self.exp = [""]
         self.embeds, self.rotations, self.aligns = [], {}, []
         self.images, self.masks, self.latents = {}, {}, {}  # path -> (tensor, row) / tensor [1,1,h,w] / {name: tensor}
@@ -822,6 +831,15 @@ class SaveAllRecorder:
             for k, (_m, paths) in enumerate(group.values()):
                 masks.update({p: (coloured, k) for p in paths})
         self._rendered = (images, masks)
+        if self.png_encoder == "device":  # the same tensors, each encoded once: (files, sizes) on the device
+            from . import _marshal as M
+            from ._runtime import lib, stream
+
+            self._encoded = {}
+            for part in self._rendered:
+                for u8, _row in part.values():
+                    if id(u8) not in self._encoded:
+                        self._encoded[id(u8)] = M.png_encode(lib(), stream(), u8, M.PNG_FILTERS["adaptive"])
         self._tick(t0, t1)
 
     def write(self):
@@ -830,6 +848,8 @@ class SaveAllRecorder:
 
         if self._rendered is None:
             raise RuntimeError("SaveAllRecorder.write before render")
+        if self.png_encoder == "device":
+            return self._write_encoded()
         t0 = self._tick()
         host = {}
 
@@ -844,6 +864,30 @@ class SaveAllRecorder:
         for p, arr in pictures.items():
             p.parent.mkdir(parents=True, exist_ok=True)
             Image.fromarray(np.ascontiguousarray(arr)).save(p)
+        for p, d in latents.items():
+            p.parent.mkdir(parents=True, exist_ok=True)
+            np.savez(p, **d)
+        if SAVE_ALL_TIMES is not None:
+            SAVE_ALL_TIMES["copy_s"] = SAVE_ALL_TIMES.get("copy_s", 0.0) + t1 - t0
+            SAVE_ALL_TIMES["encode_s"] = SAVE_ALL_TIMES.get("encode_s", 0.0) + time.time() - t1
+        return sorted(list(pictures) + list(latents))
+
+    def _write_encoded(self):
+        """`write` for png_encoder="device": per encoded tensor one copy of the files that are written, then plain writes."""
+        from .image_utils import fetch_png
+
+        t0 = self._tick()
+        rows = {}
+        for part in self._rendered:
+            for p, (u8, row) in part.items():
+                rows.setdefault(id(u8), []).append(row)
+        files = {key: fetch_png(*self._encoded[key], rows=r) for key, r in rows.items()}
+        pictures = {p: files[id(u8)][row] for part in self._rendered for p, (u8, row) in part.items()}
+        latents = {p: {k: v.cpu().numpy() for k, v in d.items()} for p, d in self.latents.items()}
+        t1 = self._tick()
+        for p, data in pictures.items():
+            p.parent.mkdir(parents=True, exist_ok=True)
+            p.write_bytes(data)
         for p, d in latents.items():
             p.parent.mkdir(parents=True, exist_ok=True)
             np.savez(p, **d)
@@ -1052,7 +1096,8 @@ class HairFast:
             set_seed(seed_)
             if not save_all:
                 return self._swap_from_tensors(*images, exp_name=exp_name, **kwargs), None
-            rec = SaveAllRecorder(self.args.save_all_dir)  # a fresh one per attempt: the files are those of the run returned
+            # a fresh one per attempt: the files are those of the run returned
+            rec = SaveAllRecorder(self.args.save_all_dir, getattr(self.args, "png_encoder", "pil"))
             rec.begin([exp_name])
             final = self._swap_from_tensors(*images, exp_name=exp_name, **dict(kwargs, recorder=rec))
             rec.render(self.net.generator)  # after the last draw of the swap proper
@@ -1139,7 +1184,7 @@ class HairFast:
 
         def run():
             set_seed(seed_)
-            rec = SaveAllRecorder(self.args.save_all_dir) if save_all else None
+            rec = SaveAllRecorder(self.args.save_all_dir, getattr(self.args, "png_encoder", "pil")) if save_all else None
             kw = dict(kwargs, recorder=rec) if save_all else kwargs
             res = [None] * len(prepared)
             if plain:

@@ -30,7 +30,8 @@ Deviations from the reference, by design:
 Also here: the image side of `--save_all` (utils/save_utils.py:12-30) - `to_bytes` (ToPILImage's / save_image's bytes of
 float images, hf_image_to_bytes_f32), `labels_to_rgb` (`mask_to_rgb(pred, 0)`, hf_labels_to_rgb_i64) and `save_image`
 (main.py:44's torchvision call for one image).  The bytes are made on the device: a quarter of the float image crosses to
-the host.
+the host.  `encode_png` / `save_images` / `save_image(encoder="device")` make the PNG file itself on the device
+(hf_png_encode_u8): only the compressed bytes cross and no zlib runs on the host.
 """
 from types import SimpleNamespace
 
@@ -228,10 +229,87 @@ def labels_to_rgb(labels):
     return M.labels_to_rgb(lib(), stream(), labels, label_palette(labels.device), UNKNOWN_LABEL)
 
 
-def save_image(image, path, value_range=(0, 1), rounding="nearest", **pil_kwargs):
+def save_image(image, path, value_range=(0, 1), rounding="nearest", encoder="pil", **pil_kwargs):
     """`torchvision.utils.save_image(image, path)` for ONE image (main.py:44) without torchvision: fp32 [3,H,W] (or
-    [1,3,H,W]) in [0,1] on the GPU -> `to_bytes(value_range, rounding)` and PIL.  `pil_kwargs` go to `Image.save`."""
+    [1,3,H,W]) in [0,1] on the GPU -> `to_bytes(value_range, rounding)`, then `encoder`: "pil" - the bytes go to the host and
+    PIL (zlib) makes the file, `pil_kwargs` go to `Image.save`; "device" - `encode_png` makes the file on the GPU and only
+    its bytes cross (no `pil_kwargs`)."""
+    if encoder not in ENCODERS:
+        raise ValueError(f"encoder must be one of {ENCODERS}; got {encoder!r}")
+    if encoder == "device" and pil_kwargs:
+        raise TypeError(f"save_image(encoder='device') takes no PIL arguments; got {sorted(pil_kwargs)}")
     x = _images_4d(image, "save_image")
     if x.shape[0] != 1:
         raise ValueError(f"save_image writes one image; got a batch of {x.shape[0]}")
-    _to_pil(to_bytes(x, value_range, rounding, "hwc")[0]).save(path, **pil_kwargs)
+    if encoder == "device":
+        save_images(x, [path], value_range, rounding, "device")
+    else:
+        _to_pil(to_bytes(x, value_range, rounding, "hwc")[0]).save(path, **pil_kwargs)
+
+
+# ---------------------------------------------------------------------------------------------
+# PNG files made on the device (csrc/png.h)
+# ---------------------------------------------------------------------------------------------
+ENCODERS = ("pil", "device")
+PNG_FILTERS = M.PNG_FILTERS
+
+
+def fetch_png(files, sizes, rows=None):
+    """The files of `M.png_encode` on the host: {row: bytes} for `rows` (default: all).  One synchronisation (the copy of
+    `sizes`), then one copy of exactly the encoded bytes."""
+    n = sizes.cpu().tolist()
+    rows = list(range(len(n))) if rows is None else sorted(set(rows))
+    parts = [files[r, :n[r]] for r in rows]
+    host = (parts[0] if len(parts) == 1 else torch.cat(parts)).cpu().numpy().tobytes()
+    out, pos = {}, 0
+    for r in rows:
+        out[r] = host[pos:pos + n[r]]
+        pos += n[r]
+    return out
+
+
+def encode_png(images, filter="adaptive"):
+    """uint8 images on the GPU - [B,H,W,3], [B,H,W,1], [B,H,W], [H,W,3] or [H,W] - -> list of B complete PNG files as
+    `bytes` (a single image: `bytes`), RGB or greyscale, encoded on the device (hf_png_encode_u8: row filters, one
+    dynamic-Huffman block with distance-1 matches per group of rows, checksums).  `filter`: "none",
+    "sub", "up" on every row, or "adaptive" (per row the type with the smallest sum of absolute residuals).  A file decodes
+    to exactly the input bytes; it is not the file PIL would write.  One encode call, one synchronisation, one copy."""
+    if not isinstance(images, torch.Tensor):
+        raise TypeError(f"encode_png: expected a torch.Tensor; got {type(images)}")
+    if images.dtype != torch.uint8:
+        raise TypeError(f"encode_png: expected uint8 images; got {images.dtype}")
+    if filter not in PNG_FILTERS:
+        raise ValueError(f"filter must be one of {tuple(PNG_FILTERS)}; got {filter!r}")
+    if images.ndim == 2:
+        x, single = images[None, :, :, None], True
+    elif images.ndim == 3 and images.shape[-1] == 3:  # [H,W,3]; a batch of three-pixel-wide grey images goes in as [B,H,3,1]
+        x, single = images[None], True
+    elif images.ndim == 3:
+        x, single = images[..., None], False
+    elif images.ndim == 4 and images.shape[-1] in (1, 3):
+        x, single = images, False
+    else:
+        raise ValueError(f"encode_png: expected [B,H,W,3], [B,H,W,1], [B,H,W], [H,W,3] or [H,W]; got {tuple(images.shape)}")
+    require_gpu(x)
+    files = fetch_png(*M.png_encode(lib(), stream(), x, PNG_FILTERS[filter]))
+    return files[0] if single else [files[k] for k in range(x.shape[0])]
+
+
+def save_images(images, paths, value_range=(0, 1), rounding="nearest", encoder="device"):
+    """A batch of float images fp32 [B,3,H,W] on the GPU to `paths` (one per image) as PNG files: ONE `to_bytes` call and,
+    with encoder="device", ONE `encode_png` call; "pil" encodes each image on the host."""
+    if encoder not in ENCODERS:
+        raise ValueError(f"encoder must be one of {ENCODERS}; got {encoder!r}")
+    x = _images_4d(images, "save_images")
+    paths = list(paths)
+    if len(paths) != x.shape[0]:
+        raise ValueError(f"save_images: {x.shape[0]} images, {len(paths)} paths")
+    u8 = to_bytes(x, value_range, rounding, "hwc")
+    if encoder == "device":
+        for path, data in zip(paths, encode_png(u8)):
+            with open(path, "wb") as fh:
+                fh.write(data)
+    else:
+        host = u8.cpu()
+        for k, path in enumerate(paths):
+            _to_pil(host[k]).save(path)

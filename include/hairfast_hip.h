@@ -614,6 +614,25 @@ int hf_image_to_bytes_f32(unsigned char *out, const float *in, int batch, int h,
 int hf_labels_to_rgb_i64(unsigned char *out, const long long *labels, long long n_pixels, const unsigned char *palette,
                          int n_colors, int unknown_label, void *stream);
 
+/* ---- a PNG encoder on the device (csrc/png.h) ----
+ * in: u8 [batch, h, w, channels] interleaved, channels 1 (grey) or 3 (RGB).  Image b's complete PNG file (signature, IHDR,
+ * one IDAT, IEND) is written to out + b * out_stride and its length to sizes[b] (device memory, 8-byte aligned); nothing is
+ * written outside [out + b * out_stride, + hf_png_bound).  The image is cut into segments of hf_png_segment_rows rows, each
+ * one deflate block (dynamic Huffman over literals and distance-1 matches, or stored where that is not smaller) ending on a
+ * byte boundary.  filter: 0 none, 1 sub, 2 up on every row; 3 adaptive (per row the type of None, Sub, Up, Average, Paeth
+ * with the smallest sum of absolute signed residuals, lowest type on ties).  The bytes of image b depend on that image, the
+ * shape and the filter only.  Three asynchronous launches on `stream`; `in` is not written.
+ * hf_png_bound: the largest file for the shape, h * (w * channels + 1) + 5 * segments + 68; 0 for a shape the encoder does
+ * not take (channels not 1 or 3, a non-positive dimension, w * channels + 1 > 24640, a file of 2 GiB or more);
+ * hf_png_segment_rows and hf_png_workspace_bytes are 0 for those too.  Host only.
+ * HF_E_INVALID: a null pointer, such a shape, filter outside 0..3, batch outside 1..65535, out_stride < hf_png_bound, a
+ * workspace that is not 16-byte aligned.  HF_E_WORKSPACE: workspace_bytes < hf_png_workspace_bytes. */
+long long hf_png_bound(int h, int w, int channels);
+int hf_png_segment_rows(int h, int w, int channels);
+long long hf_png_workspace_bytes(int batch, int h, int w, int channels);
+int hf_png_encode_u8(unsigned char *out, long long out_stride, long long *sizes, const unsigned char *in, int batch, int h,
+                     int w, int channels, int filter, void *workspace, long long workspace_bytes, void *stream);
+
 /* ---- PostProcessModel's latent branch (models/Encoders.py:13-32, 119-131) ----
  * F.layer_norm over the last `dim` elements of each of `rows` rows (biased variance, eps inside the sqrt):
  * gamma / beta [dim] = elementwise affine (both NULL: LayerNorm(elementwise_affine=False), :19), lrelu != 0

@@ -8,7 +8,10 @@ line (kept as profiles/save_all_bench.json):
 * one swap with args.save_all on and off (median wall seconds, device-synchronised), and the recorder's share split into
   the two extra generator calls, quantisation + colouring, the copy to the host, and PNG / npz encoding on the host.
 
-usage: python tools/bench_save_all.py [--reps N] [--swaps N]"""
+`--png_encoder device` runs the swap with the recorder's PNG files made on the GPU (csrc/png.h): "bytes_s" then holds the
+encodes as well, "copy_s" the copy of the encoded files and "encode_s" only the file writes.
+
+usage: python tools/bench_save_all.py [--reps N] [--swaps N] [--png_encoder {pil,device}]"""
 import argparse
 import json
 import os
@@ -45,10 +48,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--swaps", type=int, default=5)
+    ap.add_argument("--png_encoder", choices=("pil", "device"), default="pil")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_save_all needs a GPU"
     dev = torch.device("cuda:0")
-    res = {"metric": "save_all", "device": torch.cuda.get_device_name(0)}
+    res = {"metric": "save_all", "device": torch.cuda.get_device_name(0), "png_encoder": a.png_encoder}
     # ---- the kernels ----
     x = torch.rand(13, 3, 1024, 1024, generator=torch.Generator().manual_seed(0)).mul(2).sub(1).to(dev)
     nbytes = x.numel() * 5  # 4 read + 1 written per element
@@ -77,6 +81,7 @@ def main():
     images = [torch.randint(0, 256, (3, 1024, 1024), dtype=torch.uint8, generator=g).to(dev) for _ in range(3)]
     out_dir = tempfile.mkdtemp(prefix="save_all_bench_")
     hf.args.save_all_dir = HS.Path(out_dir)
+    hf.args.png_encoder = a.png_encoder
 
     def swap_s(save_all, times=None):
         hf.args.save_all = save_all
