@@ -451,7 +451,9 @@ def paste_back(photo, result, landmarks, *, mask=None, feather=0.1, output_size=
     mask: optional crop-space [output_size, output_size] weights (uint8, or float in [0,1]) that multiply the feather -
     e.g. a hair mask; feather: the share of the crop's side over which the square fades out at its edges.
     photo / result / landmarks (and mask) may be lists of equal length: one launch per photograph, a list is returned.
-    -> float [3,H,W] in [0,1] on the device (uint8 with return_tensors=False)."""
+    -> float [3,H,W] in [0,1] on the device (uint8 with return_tensors=False).  To write it as a JPEG without the pixels
+    crossing to the host: `image_utils.encode_jpeg(pasted_u8.permute(1, 2, 0))` for the uint8 form, or
+    `image_utils.save_image(pasted, path, encoder="device", format="jpeg")` for the float one."""
     many = isinstance(photo, (list, tuple))
     photos = list(photo) if many else [photo]
     results = list(result) if many else [result]

@@ -874,14 +874,14 @@ class SaveAllRecorder:
 
     def _write_encoded(self):
         """`write` for png_encoder="device": per encoded tensor one copy of the files that are written, then plain writes."""
-        from .image_utils import fetch_png
+        from .image_utils import fetch_files
 
         t0 = self._tick()
         rows = {}
         for part in self._rendered:
             for p, (u8, row) in part.items():
                 rows.setdefault(id(u8), []).append(row)
-        files = {key: fetch_png(*self._encoded[key], rows=r) for key, r in rows.items()}
+        files = {key: fetch_files(*self._encoded[key], rows=r) for key, r in rows.items()}
         pictures = {p: files[id(u8)][row] for part in self._rendered for p, (u8, row) in part.items()}
         latents = {p: {k: v.cpu().numpy() for k, v in d.items()} for p, d in self.latents.items()}
         t1 = self._tick()

@@ -31,7 +31,8 @@ Also here: the image side of `--save_all` (utils/save_utils.py:12-30) - `to_byte
 float images, hf_image_to_bytes_f32), `labels_to_rgb` (`mask_to_rgb(pred, 0)`, hf_labels_to_rgb_i64) and `save_image`
 (main.py:44's torchvision call for one image).  The bytes are made on the device: a quarter of the float image crosses to
 the host.  `encode_png` / `save_images` / `save_image(encoder="device")` make the PNG file itself on the device
-(hf_png_encode_u8): only the compressed bytes cross and no zlib runs on the host.
+(hf_png_encode_u8): only the compressed bytes cross and no zlib runs on the host.  `encode_jpeg` and `format="jpeg"` do the
+same for JPEG (hf_jpeg_encode_u8): the file Pillow's libjpeg would write, without the pixels crossing to the host.
 """
 from types import SimpleNamespace
 
@@ -229,22 +230,26 @@ def labels_to_rgb(labels):
     return M.labels_to_rgb(lib(), stream(), labels, label_palette(labels.device), UNKNOWN_LABEL)
 
 
-def save_image(image, path, value_range=(0, 1), rounding="nearest", encoder="pil", **pil_kwargs):
+def save_image(image, path, value_range=(0, 1), rounding="nearest", encoder="pil", format=None, quality=75,
+               subsampling="4:2:0", **pil_kwargs):
     """`torchvision.utils.save_image(image, path)` for ONE image (main.py:44) without torchvision: fp32 [3,H,W] (or
     [1,3,H,W]) in [0,1] on the GPU -> `to_bytes(value_range, rounding)`, then `encoder`: "pil" - the bytes go to the host and
-    PIL (zlib) makes the file, `pil_kwargs` go to `Image.save`; "device" - `encode_png` makes the file on the GPU and only
-    its bytes cross (no `pil_kwargs`)."""
+    PIL makes the file, `pil_kwargs` go to `Image.save`; "device" - `encode_png` / `encode_jpeg` makes the file on the GPU and
+    only its bytes cross (no `pil_kwargs`).  `format`: None - PNG from the device encoder whatever the suffix, PIL chooses by
+    the suffix; "jpeg" - baseline JPEG of `quality` and `subsampling` with one restart interval per MCU row, the same file
+    from both encoders (`save_images` has the details)."""
     if encoder not in ENCODERS:
         raise ValueError(f"encoder must be one of {ENCODERS}; got {encoder!r}")
     if encoder == "device" and pil_kwargs:
         raise TypeError(f"save_image(encoder='device') takes no PIL arguments; got {sorted(pil_kwargs)}")
+    _check_format(format, quality, subsampling)
     x = _images_4d(image, "save_image")
     if x.shape[0] != 1:
         raise ValueError(f"save_image writes one image; got a batch of {x.shape[0]}")
     if encoder == "device":
-        save_images(x, [path], value_range, rounding, "device")
+        save_images(x, [path], value_range, rounding, "device", format, quality, subsampling)
     else:
-        _to_pil(to_bytes(x, value_range, rounding, "hwc")[0]).save(path, **pil_kwargs)
+        _to_pil(to_bytes(x, value_range, rounding, "hwc")[0]).save(path, **_pil_format(format, quality, subsampling), **pil_kwargs)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -254,9 +259,36 @@ ENCODERS = ("pil", "device")
 PNG_FILTERS = M.PNG_FILTERS
 
 
-def fetch_png(files, sizes, rows=None):
-    """The files of `M.png_encode` on the host: {row: bytes} for `rows` (default: all).  One synchronisation (the copy of
-    `sizes`), then one copy of exactly the encoded bytes."""
+FORMATS = (None, "jpeg")
+JPEG_SUBSAMPLINGS = M.JPEG_SUBSAMPLINGS
+
+
+def _check_format(format, quality, subsampling):
+    if format not in FORMATS:
+        raise ValueError(f"format must be one of {FORMATS}; got {format!r}")
+    if format is None and (quality != 75 or subsampling != "4:2:0"):
+        raise TypeError("quality and subsampling belong to format='jpeg'")
+    if format == "jpeg":
+        _check_jpeg(quality, subsampling)
+
+
+def _check_jpeg(quality, subsampling):
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise ValueError(f"quality must be an integer in 1..100; got {quality!r}")
+    if subsampling not in JPEG_SUBSAMPLINGS:
+        raise ValueError(f"subsampling must be one of {tuple(JPEG_SUBSAMPLINGS)}; got {subsampling!r}")
+
+
+def _pil_format(format, quality, subsampling):
+    """`Image.save` arguments with which PIL writes the file the device encoder writes."""
+    if format is None:
+        return {}
+    return {"format": "JPEG", "quality": quality, "subsampling": subsampling, "restart_marker_rows": 1}
+
+
+def fetch_files(files, sizes, rows=None):
+    """The files of `M.png_encode` / `M.jpeg_encode` on the host: {row: bytes} for `rows` (default: all).  One
+    synchronisation (the copy of `sizes`), then one copy of exactly the encoded bytes."""
     n = sizes.cpu().tolist()
     rows = list(range(len(n))) if rows is None else sorted(set(rows))
     parts = [files[r, :n[r]] for r in rows]
@@ -268,48 +300,73 @@ def fetch_png(files, sizes, rows=None):
     return out
 
 
+def _u8_images(images, what):
+    """The input forms of encode_png / encode_jpeg -> (uint8 [B,H,W,1|3], whether it was a single image)."""
+    if not isinstance(images, torch.Tensor):
+        raise TypeError(f"{what}: expected a torch.Tensor; got {type(images)}")
+    if images.dtype != torch.uint8:
+        raise TypeError(f"{what}: expected uint8 images; got {images.dtype}")
+    if images.ndim == 2:
+        return images[None, :, :, None], True
+    if images.ndim == 3 and images.shape[-1] == 3:  # [H,W,3]; a batch of three-pixel-wide grey images goes in as [B,H,3,1]
+        return images[None], True
+    if images.ndim == 3:
+        return images[..., None], False
+    if images.ndim == 4 and images.shape[-1] in (1, 3):
+        return images, False
+    raise ValueError(f"{what}: expected [B,H,W,3], [B,H,W,1], [B,H,W], [H,W,3] or [H,W]; got {tuple(images.shape)}")
+
+
 def encode_png(images, filter="adaptive"):
     """uint8 images on the GPU - [B,H,W,3], [B,H,W,1], [B,H,W], [H,W,3] or [H,W] - -> list of B complete PNG files as
     `bytes` (a single image: `bytes`), RGB or greyscale, encoded on the device (hf_png_encode_u8: row filters, one
     dynamic-Huffman block with distance-1 matches per group of rows, checksums).  `filter`: "none",
     "sub", "up" on every row, or "adaptive" (per row the type with the smallest sum of absolute residuals).  A file decodes
     to exactly the input bytes; it is not the file PIL would write.  One encode call, one synchronisation, one copy."""
-    if not isinstance(images, torch.Tensor):
-        raise TypeError(f"encode_png: expected a torch.Tensor; got {type(images)}")
-    if images.dtype != torch.uint8:
-        raise TypeError(f"encode_png: expected uint8 images; got {images.dtype}")
+    x, single = _u8_images(images, "encode_png")
     if filter not in PNG_FILTERS:
         raise ValueError(f"filter must be one of {tuple(PNG_FILTERS)}; got {filter!r}")
-    if images.ndim == 2:
-        x, single = images[None, :, :, None], True
-    elif images.ndim == 3 and images.shape[-1] == 3:  # [H,W,3]; a batch of three-pixel-wide grey images goes in as [B,H,3,1]
-        x, single = images[None], True
-    elif images.ndim == 3:
-        x, single = images[..., None], False
-    elif images.ndim == 4 and images.shape[-1] in (1, 3):
-        x, single = images, False
-    else:
-        raise ValueError(f"encode_png: expected [B,H,W,3], [B,H,W,1], [B,H,W], [H,W,3] or [H,W]; got {tuple(images.shape)}")
     require_gpu(x)
-    files = fetch_png(*M.png_encode(lib(), stream(), x, PNG_FILTERS[filter]))
+    files = fetch_files(*M.png_encode(lib(), stream(), x, PNG_FILTERS[filter]))
     return files[0] if single else [files[k] for k in range(x.shape[0])]
 
 
-def save_images(images, paths, value_range=(0, 1), rounding="nearest", encoder="device"):
-    """A batch of float images fp32 [B,3,H,W] on the GPU to `paths` (one per image) as PNG files: ONE `to_bytes` call and,
-    with encoder="device", ONE `encode_png` call; "pil" encodes each image on the host."""
+def encode_jpeg(images, quality=75, subsampling="4:2:0"):
+    """uint8 images on the GPU - [B,H,W,3], [B,H,W,1], [B,H,W], [H,W,3] or [H,W], the forms `encode_png` takes; the
+    uint8 photograph of `paste_back(..., return_tensors=False)` is planar [3,H,W] and goes in as its `.permute(1, 2, 0)` view,
+    the float one through `to_bytes(x, (0, 1), "nearest")` or `save_image(format="jpeg")` - -> list of B complete JPEG files as `bytes` (a single
+    image: `bytes`), encoded on the device (hf_jpeg_encode_u8).  Baseline JFIF, YCbCr or greyscale,
+    `quality` 1..100 with libjpeg's tables, `subsampling` "4:4:4", "4:2:2" or "4:2:0" (no effect on grey images), the standard
+    Huffman tables, one restart interval per MCU row: byte for byte the file of
+    `PIL.Image.save(format="JPEG", quality=quality, subsampling=subsampling, restart_marker_rows=1)`.  One encode call, one
+    synchronisation, one copy of exactly the encoded bytes."""
+    x, single = _u8_images(images, "encode_jpeg")
+    _check_jpeg(quality, subsampling)
+    require_gpu(x)
+    files = fetch_files(*M.jpeg_encode(lib(), stream(), x, quality, JPEG_SUBSAMPLINGS[subsampling]))
+    return files[0] if single else [files[k] for k in range(x.shape[0])]
+
+
+def save_images(images, paths, value_range=(0, 1), rounding="nearest", encoder="device", format=None, quality=75,
+                subsampling="4:2:0"):
+    """A batch of float images fp32 [B,3,H,W] on the GPU to `paths` (one per image): ONE `to_bytes` call and, with
+    encoder="device", ONE `encode_png` / `encode_jpeg` call; "pil" encodes each image on the host.  `format=None`: PNG files
+    from the device encoder whatever the suffix, PIL chooses by the suffix.  `format="jpeg"`: JPEG of `quality` (1..100) and
+    `subsampling` ("4:4:4", "4:2:2", "4:2:0"); PIL is then called with restart_marker_rows=1, so both encoders write the same
+    file.  `quality` or `subsampling` other than the defaults without format="jpeg" is a TypeError."""
     if encoder not in ENCODERS:
         raise ValueError(f"encoder must be one of {ENCODERS}; got {encoder!r}")
+    _check_format(format, quality, subsampling)
     x = _images_4d(images, "save_images")
     paths = list(paths)
     if len(paths) != x.shape[0]:
         raise ValueError(f"save_images: {x.shape[0]} images, {len(paths)} paths")
     u8 = to_bytes(x, value_range, rounding, "hwc")
     if encoder == "device":
-        for path, data in zip(paths, encode_png(u8)):
+        for path, data in zip(paths, encode_png(u8) if format is None else encode_jpeg(u8, quality, subsampling)):
             with open(path, "wb") as fh:
                 fh.write(data)
     else:
         host = u8.cpu()
         for k, path in enumerate(paths):
-            _to_pil(host[k]).save(path)
+            _to_pil(host[k]).save(path, **_pil_format(format, quality, subsampling))

@@ -633,6 +633,33 @@ long long hf_png_workspace_bytes(int batch, int h, int w, int channels);
 int hf_png_encode_u8(unsigned char *out, long long out_stride, long long *sizes, const unsigned char *in, int batch, int h,
                      int w, int channels, int filter, void *workspace, long long workspace_bytes, void *stream);
 
+/* ---- a baseline JPEG encoder on the device (csrc/jpeg.h) ----
+ * in: u8 [batch, h, w, channels] interleaved, channels 1 (grey) or 3 (RGB).  Image b's complete JFIF file is written to
+ * out + b * out_stride and its length to sizes[b] (device memory, 8-byte aligned); nothing is written outside
+ * [out + b * out_stride, + hf_jpeg_bound).  The file is byte for byte what libjpeg(-turbo) writes with
+ * jpeg_set_quality(quality, force_baseline), the "islow" DCT, the Annex K Huffman tables and one restart interval per MCU
+ * row - Pillow's Image.save(format="JPEG", quality=, subsampling=, restart_marker_rows=1): SOI, APP0 (JFIF 1.01, density
+ * 1x1 without unit), DQT, SOF0, DHT, DRI, SOS, the intervals with RSTm between them, EOI.  quality: 1..100.  subsampling:
+ * 0 (4:4:4), 1 (4:2:2), 2 (4:2:0); one channel is coded alike for all three.  The bytes of image b depend on that image,
+ * the shape, the quality and the subsampling only.  Three asynchronous launches on `stream`; `in` is not written; the
+ * quantisation tables, the Huffman codes and the header are computed on the host side of the call.
+ * hf_jpeg_bound: the largest file for the shape, from the code tables: a block is at most 22 + 63 * 26 = 1660 bits (DC: 11
+ * code bits, 11 value bits; each AC coefficient: 16 code bits, 10 value bits), an interval (the blocks of one MCU row, padded
+ * to a byte) at most doubles by byte stuffing, plus the header (334 bytes grey, 629 RGB), a marker behind every interval.
+ * 0 for a shape the encoder does not take (channels not 1 or 3, a dimension outside 1..65535, subsampling outside 0..2, a
+ * file of 2 GiB or more); hf_jpeg_workspace_bytes is 0 for those and for batch <= 0.  hf_jpeg_chunk_mcus: the MCUs the
+ * entropy kernel codes per pass over an interval (256 / blocks per MCU; 0 for channels or subsampling it does not take).
+ * Host only.
+ * HF_E_INVALID: a null pointer, such a shape, quality outside 1..100, batch outside 1..65535, out_stride < hf_jpeg_bound,
+ * a workspace that is not 16-byte aligned.  HF_E_WORKSPACE: workspace_bytes < hf_jpeg_workspace_bytes.  Nothing is launched
+ * when the call refuses. */
+long long hf_jpeg_bound(int h, int w, int channels, int subsampling);
+int hf_jpeg_chunk_mcus(int channels, int subsampling);
+long long hf_jpeg_workspace_bytes(int batch, int h, int w, int channels, int subsampling);
+int hf_jpeg_encode_u8(unsigned char *out, long long out_stride, long long *sizes, const unsigned char *in, int batch, int h,
+                      int w, int channels, int quality, int subsampling, void *workspace, long long workspace_bytes,
+                      void *stream);
+
 /* ---- PostProcessModel's latent branch (models/Encoders.py:13-32, 119-131) ----
  * F.layer_norm over the last `dim` elements of each of `rows` rows (biased variance, eps inside the sqrt):
  * gamma / beta [dim] = elementwise affine (both NULL: LayerNorm(elementwise_affine=False), :19), lrelu != 0
