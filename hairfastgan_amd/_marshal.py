@@ -1532,3 +1532,36 @@ def jpeg_encode(lib, st, images, quality=75, subsampling=2):
     check(lib, lib.hf_jpeg_encode_u8(_p(files), stride, _p(sizes), _p(images), b, h, w, c, quality, subsampling, _p(ws), ws.numel() * 8,
                                      st), "hf_jpeg_encode_u8")
     return files, sizes
+
+
+JPEG_TABLE_BYTES = 2048  # per file: quantisation tables uint16 [3][64], six Huffman tables of 16 counts + 256 symbols
+JPEG_DECODE_ERRORS = {1: "truncated scan (fewer MCUs than the header implies, or no marker ends it)",
+                      2: "an unexpected marker in the scan", 3: "a block of more than 64 coefficients",
+                      4: "a code that is not in the Huffman table", 5: "a DC difference of more than 11 bits"}
+
+
+def jpeg_decode(lib, st, scans, offsets, max_scan_bytes, tables, h, w, components, hs, vs, restart_interval, out_channels=3,
+                u8=True, f32=False, sub_bytes=0):
+    """The scans of B files of one geometry (csrc/jpeg_decode.h) -> (uint8 [B,H,W,out_channels] or None, float32
+    [B,out_channels,H,W] or None, status int32 [B,2]) on the scans' device.  scans: uint8 [N]; offsets: int64 [B+1];
+    tables: uint8 [B,2048] (the layout include/hairfast_hip.h states).  Nothing is synchronised: the caller reads status."""
+    if scans.dtype != torch.uint8 or tables.dtype != torch.uint8 or offsets.dtype != torch.int64:
+        raise TypeError(f"expected uint8 scans and tables, int64 offsets; got {scans.dtype}, {tables.dtype}, {offsets.dtype}")
+    if tables.ndim != 2 or tables.shape[1] != JPEG_TABLE_BYTES or offsets.ndim != 1 or offsets.numel() != tables.shape[0] + 1:
+        raise ValueError(f"expected tables [B,{JPEG_TABLE_BYTES}] and offsets [B+1]; got {tuple(tables.shape)}, {tuple(offsets.shape)}")
+    if not (u8 or f32):
+        raise ValueError("one of u8 and f32 must be asked for")
+    if not (scans.is_contiguous() and tables.is_contiguous() and offsets.is_contiguous()) or scans.numel() == 0:
+        raise ValueError("scans, offsets and tables must be contiguous and not empty")
+    b, dev = tables.shape[0], scans.device
+    ws_bytes = lib.hf_jpeg_decode_workspace_bytes(b, h, w, components, hs, vs, restart_interval, int(max_scan_bytes))
+    if ws_bytes <= 0:
+        raise ValueError(f"hf_jpeg_decode_u8 does not take {b} files of {h}x{w}, {components} components, sampling {hs}x{vs}")
+    out = torch.empty((b, h, w, out_channels), dtype=torch.uint8, device=dev) if u8 else None
+    outf = torch.empty((b, out_channels, h, w), dtype=torch.float32, device=dev) if f32 else None
+    status = torch.empty((b, 2), dtype=torch.int32, device=dev)
+    ws = torch.empty((ws_bytes + 15) // 16 * 2, dtype=torch.int64, device=dev)
+    check(lib, lib.hf_jpeg_decode_u8(_p(out) if u8 else None, _p(outf) if f32 else None, _p(status), _p(scans), scans.numel(), _p(offsets),
+                                     int(max_scan_bytes), _p(tables), b, h, w, components, hs, vs, restart_interval, out_channels,
+                                     int(sub_bytes), _p(ws), ws.numel() * 8, st), "hf_jpeg_decode_u8")
+    return out, outf, status

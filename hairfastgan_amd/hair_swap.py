@@ -65,6 +65,8 @@ def get_parser():
     parser.add_argument("--save_all", action="store_true")
     parser.add_argument("--png_encoder", choices=("pil", "device"), default="pil",
                         help="who makes the PNG files of --save_all: PIL (zlib on the host) or the GPU (image_utils.encode_png)")
+    parser.add_argument("--image_decoder", choices=("pil", "device"), default="pil",
+                        help="who decodes JPEG files given as paths: PIL (libjpeg on the host) or the GPU (image_utils.decode_jpeg)")
     parser.add_argument("--mixing", type=float, default=0.95)
     parser.add_argument("--smooth", type=int, default=5)
     parser.add_argument("--rotate_checkpoint", type=str, default="pretrained_models/Rotate/rotate_best.pth")
@@ -157,10 +159,19 @@ def _same_content(a, b, fa, fb):
     return torch.allclose(fa, fb)
 
 
-def equal_replacer(images):
-    """utils/image_utils.py:14-24: uint8 -> [0,1]; images with equal content become the same object."""
+def _unit_exact(im):
+    """uint8 on the GPU -> float32 byte / 255 with a true division: the bits of the CPU's `tensor / 255`."""
+    from . import _marshal as M
+    from ._runtime import lib, stream
+
+    return M.u8_to_unit(lib(), stream(), im)
+
+
+def equal_replacer(images, exact=()):
+    """utils/image_utils.py:14-24: uint8 -> [0,1]; images with equal content become the same object.  `exact`: ids of
+    uint8 images on the GPU (files the device decoder read) whose division must give the CPU's bits."""
     raw = list(images)
-    images = [im / 255 if im.dtype is torch.uint8 else im for im in raw]
+    images = [(_unit_exact(im) if id(im) in exact else im / 255) if im.dtype is torch.uint8 else im for im in raw]
     for i in range(len(images)):
         for j in range(i + 1, len(images)):
             if images[i].shape == images[j].shape and _same_content(raw[i], raw[j], images[i], images[j]):
@@ -169,7 +180,7 @@ def equal_replacer(images):
     return images
 
 
-def equal_replacer_many(triples, _any_device=False):
+def equal_replacer_many(triples, _any_device=False, exact=()):
     """`equal_replacer` for the T triples of a batched pass with ONE device synchronisation instead of up to 3 T: when every
     image is an 8-bit image of one shape on one device (what `parallel.swap_many` feeds), the 3 T pair comparisons are three
     batched `!=` / `any` reductions over stacked images and one copy of their T x 3 flags to the host.  Anything else
@@ -179,13 +190,14 @@ def equal_replacer_many(triples, _any_device=False):
     batched = (len(triples) > 1 and all(len(tr) == 3 for tr in triples) and first is not None and (first.is_cuda or _any_device)
                and all(torch.is_tensor(im) and im.dtype is torch.uint8 and im.shape == first.shape and im.device == first.device for im in flat)
                and len({id(im) for im in flat}) == len(flat))
-    if not batched:
-        return [tuple(equal_replacer(list(tr))) for tr in triples]
+    n_exact = sum(id(im) in exact for im in flat)
+    if not batched or 0 < n_exact < len(flat):
+        return [tuple(equal_replacer(list(tr), exact)) for tr in triples]
     cols = [torch.stack([tr[k] for tr in triples]) for k in range(3)]
     # eight bytes per compared element where the rows allow it (the comparison is for equality only)
     wide = [c.view(torch.int64) if c.shape[-1] % 8 == 0 else c for c in cols]
     differ = torch.stack([(wide[i] != wide[j]).flatten(1).any(1) for i, j in ((0, 1), (0, 2), (1, 2))], 1).cpu()  # [T, 3]: the one sync
-    scaled = [c / 255 for c in cols]  # three launches for the 3 T divisions; a triple's images are rows of them (same bits)
+    scaled = [_unit_exact(c) if n_exact else c / 255 for c in cols]  # three launches for the 3 T divisions; a triple's images are rows of them (same bits)
     out = []
     for t in range(len(triples)):
         images = [scaled[k][t] for k in range(3)]
@@ -969,6 +981,43 @@ class HairFast:
             return _to_tensor_like_torchvision(arr.astype(np.uint8) * 255 if img.mode == "1" else arr)
         raise TypeError(f"Unsupported image format {type(img)}")
 
+    def _decode_paths(self, images, cache):
+        """args.image_decoder == "device": every distinct path among `images` whose file begins with FF D8 is decoded by
+        `image_utils.decode_jpeg` in ONE call and enters `cache` as uint8 [3,H,W] on the device, where `_as_tensor` finds it;
+        a JPEG file the device decoder does not take raises (no fallback to PIL).  -> the ids of those tensors."""
+        if getattr(self.args, "image_decoder", "pil") != "device":
+            return set()
+        from .image_utils import decode_jpeg
+
+        paths = []
+        for img in images:
+            if isinstance(img, (Path, str)) and img not in cache and img not in paths and not str(img).endswith(".npy"):
+                with open(img, "rb") as fh:
+                    if fh.read(2) == b"\xFF\xD8":
+                        paths.append(img)
+        if not paths:
+            return set()
+        for img, t in zip(paths, decode_jpeg([str(p) for p in paths], device=self.args.device)):
+            cache[img] = t.permute(2, 0, 1).contiguous()
+        return {id(cache[img]) for img in paths}
+
+    def _beside_decoded(self, images, decoded):
+        """With files decoded on the device among `images`, the CPU tensors beside them (other files, PIL images, arrays)
+        follow them there, so that one swap does not mix devices; a uint8 one joins `decoded`: its division by 255 on the
+        device is then the exact one, the CPU's bits.  Without decoded files nothing changes."""
+        if not decoded:
+            return images
+        moved, out = {}, []
+        for im in images:
+            if isinstance(im, torch.Tensor) and not im.is_cuda:
+                if id(im) not in moved:
+                    moved[id(im)] = im.to(self.args.device)
+                    if im.dtype is torch.uint8:
+                        decoded.add(id(moved[id(im)]))
+                im = moved[id(im)]
+            out.append(im)
+        return out
+
     def __init__(self, args, *, stages=None, generator_state=None, e4e_state=None, fs_state=None, e4e_latent_avg=None,
                  fs_dlatent_avg=None, pp_state=None, pp_latent_avg=None, bisenet_state=None, rotate_state=None,
                  blend_state=None, clip_image_embed=None, shape_state=None, sean_state=None, sean_mean_codes=None,
@@ -1080,10 +1129,11 @@ class HairFast:
         if paste_back and not align:
             raise ValueError("paste_back=True pastes into the photograph that align=True cropped: it needs align=True")
         cache = {}
-        images = [self._as_tensor(img, cache) for img in (face_img, shape_img, color_img)]
+        decoded = self._decode_paths((face_img, shape_img, color_img), cache)
+        images = self._beside_decoded([self._as_tensor(img, cache) for img in (face_img, shape_img, color_img)], decoded)
         if align:
             images, photos, lms = self._align_images(images, landmarks, with_inputs=True)
-        images = equal_replacer(images)
+        images = equal_replacer(images, decoded)
         set_seed(3407 if seed is None else seed)  # utils/seed.py:19-31
         if benchmark:  # utils/time.py:15-37
             torch.cuda.current_stream().synchronize()
@@ -1159,7 +1209,9 @@ class HairFast:
         if paste_back and not align:
             raise ValueError("paste_back=True pastes into the photograph that align=True cropped: it needs align=True")
         cache = {}
-        tensors = [[self._as_tensor(img, cache) for img in triple] for triple in triples]
+        triples = [tuple(triple) for triple in triples]
+        decoded = self._decode_paths([img for triple in triples for img in triple], cache)
+        tensors = [self._beside_decoded([self._as_tensor(img, cache) for img in triple], decoded) for triple in triples]
         if exp_names is None:
             exp_names = [str(t) for t in range(len(tensors))]
         exp_names = list(exp_names)
@@ -1173,7 +1225,7 @@ class HairFast:
             inputs = [self._align_images(tr, landmarks if landmarks is None or callable(landmarks) else landmarks[t], with_inputs=True)
                       for t, tr in enumerate(tensors)]
             tensors = [aligned for aligned, _, _ in inputs]
-        prepared = equal_replacer_many(tensors)
+        prepared = equal_replacer_many(tensors, exact=decoded)
         set_seed(3407 if seed is None else seed)
         # a triple that repeats an image takes the reference's shortcuts (no mixing / no second Rotate): one by one
         plain = [t for t, tr in enumerate(prepared) if len({id(x) for x in tr}) == 3]

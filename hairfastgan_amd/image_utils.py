@@ -33,6 +33,8 @@ float images, hf_image_to_bytes_f32), `labels_to_rgb` (`mask_to_rgb(pred, 0)`, h
 the host.  `encode_png` / `save_images` / `save_image(encoder="device")` make the PNG file itself on the device
 (hf_png_encode_u8): only the compressed bytes cross and no zlib runs on the host.  `encode_jpeg` and `format="jpeg"` do the
 same for JPEG (hf_jpeg_encode_u8): the file Pillow's libjpeg would write, without the pixels crossing to the host.
+`decode_jpeg` / `read_images(decoder="device")` are the way back (hf_jpeg_decode_u8): the host reads a baseline JPEG file's
+header segments, the entropy-coded bytes go to the device as they are and the pixels Pillow would return are made there.
 """
 from types import SimpleNamespace
 
@@ -370,3 +372,197 @@ def save_images(images, paths, value_range=(0, 1), rounding="nearest", encoder="
         host = u8.cpu()
         for k, path in enumerate(paths):
             _to_pil(host[k]).save(path, **_pil_format(format, quality, subsampling))
+
+
+# ---------------------------------------------------------------------------------------------
+# JPEG files decoded on the device (csrc/jpeg_decode.h)
+# ---------------------------------------------------------------------------------------------
+DECODERS = ("pil", "device")
+JPEG_MODES = ("RGB", "unchanged")
+_SOF_NAMES = {0xC1: "extended sequential", 0xC2: "progressive", 0xC3: "lossless", 0xC5: "differential sequential",
+              0xC6: "differential progressive", 0xC7: "differential lossless", 0xC9: "arithmetic coding",
+              0xCA: "arithmetic coding, progressive", 0xCB: "arithmetic coding, lossless", 0xCD: "arithmetic coding",
+              0xCE: "arithmetic coding", 0xCF: "arithmetic coding"}
+_ZIGZAG = np.array(sorted(range(64), key=lambda n: (n // 8 + n % 8, n // 8 if (n // 8 + n % 8) % 2 else n % 8)))
+
+
+def parse_jpeg_header(data):
+    """The marker segments of a JPEG file from SOI to the end of SOS (pure Python, no GPU; the scan is not looked at) ->
+    SimpleNamespace: height, width, components (1 or 3), hs, vs (luma sampling factors), restart_interval (0: none),
+    scan_start (offset of the first entropy-coded byte) and tables - the uint8 [2048] record hf_jpeg_decode_u8 reads: the
+    quantisation table of every component and its DC and AC Huffman tables.  ValueError, naming the property, for what the
+    device decoder does not take: anything but baseline sequential Huffman coding (SOF0) with 8-bit samples and 8-bit
+    quantisation tables; other than 1 or 3 components; an Adobe transform other than YCbCr; sampling other than 4:4:4,
+    4:2:2 and 4:2:0; more than one scan - and for a header that is corrupt."""
+    data = bytes(data) if not isinstance(data, bytes) else data
+    if len(data) < 4 or data[:2] != b"\xFF\xD8":
+        raise ValueError("not a JPEG file: no SOI marker")
+    pos, qt, huff, ri, sof, adobe, jfif = 2, {}, {}, 0, None, None, False
+    while True:
+        while pos + 1 < len(data) and data[pos] == 0xFF and data[pos + 1] == 0xFF:  # fill bytes
+            pos += 1
+        if pos + 4 > len(data) or data[pos] != 0xFF:
+            raise ValueError("corrupt JPEG header: no marker where one must stand")
+        marker, n = data[pos + 1], int.from_bytes(data[pos + 2:pos + 4], "big")
+        body = data[pos + 4:pos + 2 + n]
+        if n < 2 or len(body) != n - 2:
+            raise ValueError("corrupt JPEG header: a truncated segment")
+        pos += 2 + n
+        if marker == 0xDB:
+            while body:
+                if body[0] >> 4:
+                    raise ValueError("unsupported JPEG: 16-bit quantisation tables")
+                if len(body) < 65:
+                    raise ValueError("corrupt JPEG header: a short DQT segment")
+                qt[body[0] & 15] = np.frombuffer(body[1:65], np.uint8)
+                body = body[65:]
+        elif marker == 0xC4:
+            while body:
+                n_sym = sum(body[1:17]) if len(body) >= 17 else 257
+                if n_sym > 256 or len(body) < 17 + n_sym or (body[0] & 15) > 3 or (body[0] >> 4) > 1:
+                    raise ValueError("corrupt JPEG header: a bad DHT segment")
+                code = 0
+                for length in range(1, 17):
+                    code += body[length]
+                    if code > (1 << length):
+                        raise ValueError("corrupt JPEG header: an over-subscribed Huffman table")
+                    code <<= 1
+                huff[body[0]] = body[1:17 + n_sym]
+                body = body[17 + n_sym:]
+        elif marker == 0xDD:
+            if len(body) != 2:
+                raise ValueError("corrupt JPEG header: a bad DRI segment")
+            ri = int.from_bytes(body, "big")
+        elif marker == 0xC0:
+            if sof is not None:
+                raise ValueError("corrupt JPEG header: two frame headers")
+            sof = body
+        elif marker in _SOF_NAMES:
+            raise ValueError(f"unsupported JPEG: {_SOF_NAMES[marker]} (SOF{marker - 0xC0}); baseline sequential Huffman only")
+        elif marker == 0xEE and body[:5] == b"Adobe" and len(body) >= 12:
+            adobe = body[11]
+        elif marker == 0xE0 and body[:5] == b"JFIF\x00":
+            jfif = True
+        elif marker == 0xD9:
+            raise ValueError("corrupt JPEG: EOI before any scan")
+        elif marker == 0xDA:
+            break
+    if sof is None or len(sof) < 6 or len(sof) != 6 + 3 * sof[5]:
+        raise ValueError("corrupt JPEG header: no SOF0 frame header before the scan")
+    if sof[0] != 8:
+        raise ValueError(f"unsupported JPEG: {sof[0]}-bit samples")
+    h, w, nc = int.from_bytes(sof[1:3], "big"), int.from_bytes(sof[3:5], "big"), sof[5]
+    if h == 0 or w == 0:
+        raise ValueError("unsupported JPEG: a zero dimension (height given by a DNL marker)")
+    if nc not in (1, 3):
+        raise ValueError(f"unsupported JPEG: {nc} components" + (" (CMYK / YCCK)" if nc == 4 else ""))
+    ids = [sof[6 + 3 * k] for k in range(nc)]
+    samp = [(sof[7 + 3 * k] >> 4, sof[7 + 3 * k] & 15) for k in range(nc)]
+    if nc == 3 and (adobe == 0 or (adobe is None and not jfif and ids == [82, 71, 66])):
+        raise ValueError("unsupported JPEG: an RGB file (Adobe transform 0); YCbCr only")
+    if nc == 3 and adobe not in (None, 1):
+        raise ValueError(f"unsupported JPEG: Adobe colour transform {adobe}")
+    if nc == 1:
+        samp = [(1, 1)]  # a single component is not interleaved: its sampling factors mean nothing
+    elif samp[1] != (1, 1) or samp[2] != (1, 1) or samp[0] not in ((1, 1), (2, 1), (2, 2)):
+        raise ValueError("unsupported JPEG: sampling factors " + ", ".join(f"{a}x{b}" for a, b in samp) + "; 4:4:4, 4:2:2 and 4:2:0 only")
+    if len(body) < 1 or len(body) != 4 + 2 * body[0] or body[0] != nc:
+        raise ValueError("unsupported JPEG: more than one scan (a scan that does not hold every component)")
+    if (body[-3], body[-2], body[-1]) != (0, 63, 0):
+        raise ValueError("unsupported JPEG: a scan of part of the spectrum (progressive parameters)")
+    tables = np.zeros(M.JPEG_TABLE_BYTES, np.uint8)
+    q16 = tables[:384].view(np.uint16).reshape(3, 64)
+    for k in range(nc):
+        if body[1 + 2 * k] != ids[k]:
+            raise ValueError("unsupported JPEG: the scan's components are not in frame order")
+        tq, td, ta = sof[8 + 3 * k], body[2 + 2 * k] >> 4, 0x10 | (body[2 + 2 * k] & 15)
+        if tq not in qt or td not in huff or ta not in huff:
+            raise ValueError("corrupt JPEG header: a table the scan needs is not defined")
+        q16[k, _ZIGZAG] = qt[tq]
+        for slot, t in ((k, huff[td]), (3 + k, huff[ta])):
+            tables[384 + 272 * slot:384 + 272 * slot + len(t)] = np.frombuffer(t, np.uint8)
+    return SimpleNamespace(height=h, width=w, components=nc, hs=samp[0][0], vs=samp[0][1], restart_interval=ri, scan_start=pos,
+                           tables=tables)
+
+
+def _jpeg_bytes(f):
+    if isinstance(f, (bytes, bytearray, memoryview)):
+        return bytes(f)
+    if isinstance(f, str) or hasattr(f, "__fspath__"):
+        with open(f, "rb") as fh:
+            return fh.read()
+    raise TypeError(f"decode_jpeg: expected bytes or a path; got {type(f)}")
+
+
+def decode_jpeg(files, mode="RGB", dtype=torch.uint8, device="cuda", sub_bytes=0):
+    """Baseline JPEG files - `bytes`, a path, or a list of either - decoded on the device (hf_jpeg_decode_u8; DESIGN.md
+    section 4.23) -> a device tensor (a list of them for a list): uint8 [H,W,3], the pixels of
+    `PIL.Image.open(f).convert("RGB")` byte for byte ("unchanged": [H,W,1] for a grey file); with dtype=torch.float32
+    [3,H,W] ([1,H,W]) = byte / 255 in the CPU's bits.  The host reads the header segments only; files of one geometry
+    share one set of launches, all files one copy to the device and one synchronisation.  ValueError for a file the
+    decoder does not take (`parse_jpeg_header`) or whose scan is corrupt; there is no fallback to PIL."""
+    if mode not in JPEG_MODES:
+        raise ValueError(f"mode must be one of {JPEG_MODES}; got {mode!r}")
+    if dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"dtype must be torch.uint8 or torch.float32; got {dtype}")
+    single = not isinstance(files, (list, tuple))
+    datas = [_jpeg_bytes(f) for f in ([files] if single else files)]
+    if not datas:
+        return []
+    device = torch.device(device)
+    if device.type != "cuda":
+        require_gpu(torch.empty(0, device=device))
+    heads = [parse_jpeg_header(d) for d in datas]
+    groups = {}
+    for k, hd in enumerate(heads):
+        groups.setdefault((hd.height, hd.width, hd.components, hd.hs, hd.vs, hd.restart_interval), []).append(k)
+    # one host buffer: per group the offsets and the tables, then every scan; one copy
+    order = [k for ks in groups.values() for k in ks]
+    head_bytes = sum(8 * (len(ks) + 1) + 8 + M.JPEG_TABLE_BYTES * len(ks) for ks in groups.values())
+    head_bytes = (head_bytes + 15) // 16 * 16
+    total = head_bytes + sum(len(datas[k]) - heads[k].scan_start for k in order)
+    host = np.zeros(total + 16, np.uint8)
+    pos, spos, layout = 0, head_bytes, []
+    for key, ks in groups.items():
+        off = host[pos:pos + 8 * (len(ks) + 1)].view(np.int64)
+        tab_at = pos + 8 * (len(ks) + 1)
+        start = spos
+        for j, k in enumerate(ks):
+            scan = memoryview(datas[k])[heads[k].scan_start:]
+            off[j] = spos - start
+            host[spos:spos + len(scan)] = np.frombuffer(scan, np.uint8)
+            host[tab_at + j * M.JPEG_TABLE_BYTES:tab_at + (j + 1) * M.JPEG_TABLE_BYTES] = heads[k].tables
+            spos += len(scan)
+        off[len(ks)] = spos - start
+        layout.append((key, ks, pos, tab_at, start, spos, max(len(datas[k]) - heads[k].scan_start for k in ks)))
+        pos = tab_at + M.JPEG_TABLE_BYTES * len(ks)
+        pos = (pos + 7) // 8 * 8
+    blob = torch.from_numpy(host).to(device)
+    L, st = lib(), stream()
+    results, statuses = [None] * len(datas), []
+    for (h, w, nc, hs, vs, ri), ks, off_at, tab_at, start, end, longest in layout:
+        oc = 1 if (nc == 1 and mode == "unchanged") else 3
+        u8, f32, status = M.jpeg_decode(L, st, blob[start:max(end, start + 1)], blob[off_at:off_at + 8 * (len(ks) + 1)].view(torch.int64), longest,
+                                        blob[tab_at:tab_at + M.JPEG_TABLE_BYTES * len(ks)].view(len(ks), M.JPEG_TABLE_BYTES), h, w, nc, hs, vs, ri,
+                                        oc, dtype is torch.uint8, dtype is torch.float32, sub_bytes)
+        statuses.append(status[:, 0])
+        for j, k in enumerate(ks):
+            results[k] = u8[j] if dtype is torch.uint8 else f32[j]
+    codes = torch.cat(statuses).cpu().tolist()  # the one synchronisation
+    for k, code in zip(order, codes):
+        if code:
+            raise ValueError(f"corrupt JPEG scan (file {k}): {M.JPEG_DECODE_ERRORS.get(code, code)}")
+    return results[0] if single else results
+
+
+def read_images(paths, decoder="pil"):
+    """Image files -> list of uint8 [3,H,W] tensors, what `torchvision.io.read_image(path, mode=RGB)` gives: decoder="pil" on
+    the host (CPU tensors), "device" - JPEG files only - with `decode_jpeg` in one call (device tensors, views of [H,W,3])."""
+    if decoder not in DECODERS:
+        raise ValueError(f"decoder must be one of {DECODERS}; got {decoder!r}")
+    paths = list(paths)
+    if decoder == "device":
+        return [t.permute(2, 0, 1) for t in decode_jpeg(paths)]
+    from .hair_swap import _read_image_rgb
+
+    return [_read_image_rgb(p) for p in paths]

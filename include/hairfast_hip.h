@@ -660,6 +660,34 @@ int hf_jpeg_encode_u8(unsigned char *out, long long out_stride, long long *sizes
                       int w, int channels, int quality, int subsampling, void *workspace, long long workspace_bytes,
                       void *stream);
 
+/* ---- a baseline JPEG decoder on the device (csrc/jpeg_decode.h) ----
+ * hf_jpeg_decode_u8: the scans of `batch` baseline (SOF0, Huffman, 8-bit) files of ONE geometry -> uint8 images
+ * out [batch,h,w,out_channels] and / or float images out_f32 [batch,out_channels,h,w] = byte / 255 (IEEE division); either
+ * may be null, not both.  The pixels are those libjpeg-turbo returns (islow IDCT, fancy upsampling, YCbCr -> RGB), byte for
+ * byte.  The caller parses each file's marker segments (SOI to SOS) and passes, in device memory:
+ *   scans [scans_bytes]     the bytes behind each SOS segment to the end of the file; file b's are
+ *                           [scan_offsets[b], scan_offsets[b + 1]) (int64 [batch + 1], device; clamped to the buffer);
+ *                           max_scan_bytes: the longest of them (it sizes the marker search and the workspace)
+ *   tables [batch][2048]    per file: the quantisation tables of components 0..2 as uint16 [3][64] in natural (row-major)
+ *                           order; from byte 384 six Huffman tables - DC of components 0..2, then AC of components 0..2 -
+ *                           of 272 bytes each: the 16 code counts and the symbols of the DHT segment; zero padding.
+ * components: 1 (grey; hs = vs = 1) or 3 (YCbCr; luma sampling hs x vs = 1x1, 2x1 or 2x2, chroma 1x1).  restart_interval:
+ * the DRI value, 0 for none.  out_channels: 3 (grey is replicated), or 1 for components == 1.  sub_bytes: bytes per lane
+ * of the entropy decoder's self-synchronising passes, 4..64, 0 for the default.
+ * status: int32 [batch][2] (device): [b][0] is 0 or why file b's scan could not be decoded - 1 truncated (fewer MCUs
+ * than the header implies, or no marker ends the scan), 2 a marker that is not the expected RSTm, 3 a block of more than
+ * 64 coefficients, 4 a code that is not in the Huffman table, 5 a DC difference of more than 11 bits; the image is then
+ * undefined.  [b][1]: the most synchronisation passes any window of the file needed.
+ * HF_E_INVALID: a null pointer, another geometry, dimensions outside 1..65535, batch outside 1..65535, max_scan_bytes of
+ * 2 GiB or more, a misaligned workspace (16) / scan_offsets (8) / status, out_f32 (4) / tables (2).  HF_E_WORKSPACE:
+ * workspace_bytes < hf_jpeg_decode_workspace_bytes (0 for a geometry that is not taken).  Nothing is launched then. */
+long long hf_jpeg_decode_workspace_bytes(int batch, int h, int w, int components, int hs, int vs, int restart_interval,
+                                         long long max_scan_bytes);
+int hf_jpeg_decode_u8(unsigned char *out, float *out_f32, int *status, const unsigned char *scans, long long scans_bytes,
+                      const long long *scan_offsets, long long max_scan_bytes, const unsigned char *tables, int batch, int h, int w,
+                      int components, int hs, int vs, int restart_interval, int out_channels, int sub_bytes, void *workspace,
+                      long long workspace_bytes, void *stream);
+
 /* ---- PostProcessModel's latent branch (models/Encoders.py:13-32, 119-131) ----
  * F.layer_norm over the last `dim` elements of each of `rows` rows (biased variance, eps inside the sqrt):
  * gamma / beta [dim] = elementwise affine (both NULL: LayerNorm(elementwise_affine=False), :19), lrelu != 0
