@@ -1481,25 +1481,36 @@ def labels_to_rgb(lib, st, labels, palette, unknown_label=255):
 PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "adaptive": 3}
 
 
-def png_encode(lib, st, images, filter_mode=3):
-    """uint8 [B,H,W,C] (C = 1 or 3, interleaved) -> (files uint8 [B,stride], sizes int64 [B]) on the images' device: image b's
-    PNG file is files[b, :sizes[b]] (csrc/png.h).  Nothing is synchronised; stride >= hf_png_bound."""
+def _check_encode_images(images):
     if images.dtype != torch.uint8:
         raise TypeError(f"expected uint8 images; got {images.dtype}")
     if images.ndim != 4 or images.shape[3] not in (1, 3) or images.numel() == 0:
         raise ValueError(f"expected images [B,H,W,1] or [B,H,W,3] with B, H, W > 0; got {tuple(images.shape)}")
-    if filter_mode not in (0, 1, 2, 3):
-        raise ValueError(f"filter mode must be 0..3; got {filter_mode}")
-    images = images if images.is_contiguous() else images.contiguous()
+
+
+def _encode_buffers(images, bound, ws_bytes, name, limits):
+    """What png_encode and jpeg_encode allocate for checked images, the library's `bound` and workspace size: -> (contiguous
+    images, files [B,stride], stride >= bound, sizes [B], workspace).  `name`, `limits`: the entry point and what it takes."""
     b, h, w, c = images.shape
-    bound = lib.hf_png_bound(h, w, c)
     if bound <= 0:
-        raise ValueError(f"hf_png_encode_u8 does not take images of {h}x{w}x{c}: a row of at most 24639 bytes, a file below 2 GiB")
+        raise ValueError(f"{name} does not take images of {h}x{w}x{c}: {limits}")
+    images = images if images.is_contiguous() else images.contiguous()
     stride = (bound + 15) // 16 * 16
-    ws_bytes = lib.hf_png_workspace_bytes(b, h, w, c)
     files = torch.empty((b, stride), dtype=torch.uint8, device=images.device)
     sizes = torch.empty((b,), dtype=torch.int64, device=images.device)
     ws = torch.empty((ws_bytes + 15) // 16 * 2, dtype=torch.int64, device=images.device)
+    return images, files, stride, sizes, ws
+
+
+def png_encode(lib, st, images, filter_mode=3):
+    """uint8 [B,H,W,C] (C = 1 or 3, interleaved) -> (files uint8 [B,stride], sizes int64 [B]) on the images' device: image b's
+    PNG file is files[b, :sizes[b]] (csrc/png.h).  Nothing is synchronised; stride >= hf_png_bound."""
+    _check_encode_images(images)
+    if filter_mode not in (0, 1, 2, 3):
+        raise ValueError(f"filter mode must be 0..3; got {filter_mode}")
+    b, h, w, c = images.shape
+    images, files, stride, sizes, ws = _encode_buffers(images, lib.hf_png_bound(h, w, c), lib.hf_png_workspace_bytes(b, h, w, c),
+                                                       "hf_png_encode_u8", "a row of at most 24639 bytes, a file below 2 GiB")
     check(lib, lib.hf_png_encode_u8(_p(files), stride, _p(sizes), _p(images), b, h, w, c, int(filter_mode), _p(ws), ws.numel() * 8, st),
           "hf_png_encode_u8")
     return files, sizes
@@ -1511,24 +1522,15 @@ JPEG_SUBSAMPLINGS = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}
 def jpeg_encode(lib, st, images, quality=75, subsampling=2):
     """uint8 [B,H,W,C] (C = 1 or 3, interleaved) -> (files uint8 [B,stride], sizes int64 [B]) on the images' device: image b's
     JPEG file is files[b, :sizes[b]] (csrc/jpeg.h).  Nothing is synchronised; stride >= hf_jpeg_bound."""
-    if images.dtype != torch.uint8:
-        raise TypeError(f"expected uint8 images; got {images.dtype}")
-    if images.ndim != 4 or images.shape[3] not in (1, 3) or images.numel() == 0:
-        raise ValueError(f"expected images [B,H,W,1] or [B,H,W,3] with B, H, W > 0; got {tuple(images.shape)}")
+    _check_encode_images(images)
     if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
         raise ValueError(f"quality must be an integer in 1..100; got {quality!r}")
     if subsampling not in (0, 1, 2):
         raise ValueError(f"subsampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0); got {subsampling!r}")
-    images = images if images.is_contiguous() else images.contiguous()
     b, h, w, c = images.shape
-    bound = lib.hf_jpeg_bound(h, w, c, subsampling)
-    if bound <= 0:
-        raise ValueError(f"hf_jpeg_encode_u8 does not take images of {h}x{w}x{c}: dimensions of at most 65535, a file below 2 GiB")
-    stride = (bound + 15) // 16 * 16
-    ws_bytes = lib.hf_jpeg_workspace_bytes(b, h, w, c, subsampling)
-    files = torch.empty((b, stride), dtype=torch.uint8, device=images.device)
-    sizes = torch.empty((b,), dtype=torch.int64, device=images.device)
-    ws = torch.empty((ws_bytes + 15) // 16 * 2, dtype=torch.int64, device=images.device)
+    images, files, stride, sizes, ws = _encode_buffers(images, lib.hf_jpeg_bound(h, w, c, subsampling),
+                                                       lib.hf_jpeg_workspace_bytes(b, h, w, c, subsampling),
+                                                       "hf_jpeg_encode_u8", "dimensions of at most 65535, a file below 2 GiB")
     check(lib, lib.hf_jpeg_encode_u8(_p(files), stride, _p(sizes), _p(images), b, h, w, c, quality, subsampling, _p(ws), ws.numel() * 8,
                                      st), "hf_jpeg_encode_u8")
     return files, sizes

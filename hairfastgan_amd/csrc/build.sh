@@ -9,7 +9,13 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC $*"
 OBJS=""
 PIDS=""
 for f in api elementwise upfirdn2d style torgb modconv convh convh_enc encoder_ops sean vit gemm_h stem convrow; do
-  if [ ! -f $f.o ] || [ $f.hip -nt $f.o ] || [ hf_common.h -nt $f.o ] || [ conv_common.h -nt $f.o ] || { [ $f = encoder_ops ] && [ poisson.h -nt $f.o ]; } || { [ $f = encoder_ops ] && [ align.h -nt $f.o ]; } || { [ $f = encoder_ops ] && [ paste.h -nt $f.o ]; } || { [ $f = encoder_ops ] && [ export.h -nt $f.o ]; } || { [ $f = encoder_ops ] && [ png.h -nt $f.o ]; } || { [ $f = encoder_ops ] && [ jpeg.h -nt $f.o ]; } || { [ $f = encoder_ops ] && [ jpeg_decode.h -nt $f.o ]; } || [ ../../include/hairfast_hip.h -nt $f.o ]; then
+  DEPS="$f.hip hf_common.h conv_common.h ../../include/hairfast_hip.h"
+  [ $f = encoder_ops ] && DEPS="$DEPS poisson.h align.h paste.h export.h codec_common.h png.h jpeg.h jpeg_decode.h"  # what it includes
+  STALE=""
+  for d in $DEPS; do
+    [ $d -nt $f.o ] && STALE=1
+  done
+  if [ ! -f $f.o ] || [ -n "$STALE" ]; then
     $HIPCC $FLAGS -c $f.hip -o $f.o &
     PIDS="$PIDS $!"
   fi

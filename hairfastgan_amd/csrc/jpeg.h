@@ -28,9 +28,14 @@
 //   first workgroup, sizes[b] by the last.
 // Every loop is bounded by the shape; the bytes of image b depend on that image, the shape, the quality and the subsampling
 // only.
+// The 16-byte vector, the bit packer (JpegBits is its MSB-first form), the workgroup scan, the sum of the lengths before an
+// interval and the copy of a slot to the file are codec_common.h's, shared with png.h.  What encoder and decoder share is
+// stated here and used by jpeg_decode.h: the odd part of the DCT (jpeg_dct_odd), the MCU geometry (jpeg_mcus), the block of
+// an MCU -> component and place (jpeg_block_component, jpeg_luma_block_at), a coefficient of a stored block (jpeg_coef).
 #pragma once
 #include <cstdint>
 
+#include "codec_common.h"
 #include "hf_common.h"
 
 namespace {
@@ -41,10 +46,6 @@ constexpr int kJpegThreads = 256;
 // cost nothing themselves, and is no longer than 16 bits)
 constexpr int kJpegBlockBits = 11 + 11 + 63 * (16 + 10);
 constexpr int kJpegHeaderMax = 640;
-
-struct alignas(16) JpegVec16 {
-  uint32_t x, y, z, w;
-};
 
 struct JpegQuant {
   uint16_t q8[2][64];  // 8 * the quantisation step, zig-zag order: luma, chroma
@@ -90,6 +91,26 @@ static __device__ const unsigned char kJpegNatural[64] = {0,  1,  8,  16, 9,  2,
                                                           41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                                                           30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
+// The odd part that jfdctint.c and jidctint.c share: the rotations of libjpeg's z1..z5 network (CONST_BITS 13) over four
+// values, in place.  The forward pass hands in (t4, t5, t6, t7) and gets the unscaled (d7, d5, d3, d1), the inverse pass hands
+// in (d7, d5, d3, d1) and gets (t0, t1, t2, t3).
+__device__ __forceinline__ void jpeg_dct_odd(int &a, int &b, int &c, int &d) {
+  int z1 = a + d, z2 = b + c, z3 = a + c, z4 = b + d;
+  const int z5 = (z3 + z4) * 9633;
+  a *= 2446;
+  b *= 16819;
+  c *= 25172;
+  d *= 12299;
+  z1 *= -7373;
+  z2 *= -20995;
+  z3 = z3 * -16069 + z5;
+  z4 = z4 * -3196 + z5;
+  a += z1 + z3;
+  b += z2 + z4;
+  c += z2 + z3;
+  d += z1 + z4;
+}
+
 // One pass of jfdctint.c over eight values: FIRST is the row pass (results scaled up by 2^PASS1_BITS), the other the column
 // pass (that scaling removed again; the output stays scaled by 8).  CONST_BITS 13, PASS1_BITS 2.
 template <bool FIRST>
@@ -105,30 +126,36 @@ __device__ __forceinline__ void jpeg_fdct8(int &d0, int &d1, int &d2, int &d3, i
     d0 = (t10 + t11 + 2) >> 2;
     d4 = (t10 - t11 + 2) >> 2;
   }
-  int z1 = (t12 + t13) * 4433;
+  const int z1 = (t12 + t13) * 4433;
   d2 = (z1 + t13 * 6270 + kRound) >> kShift;
   d6 = (z1 - t12 * 15137 + kRound) >> kShift;
-  z1 = t4 + t7;
-  int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
-  const int z5 = (z3 + z4) * 9633;
-  t4 *= 2446;
-  t5 *= 16819;
-  t6 *= 25172;
-  t7 *= 12299;
-  z1 *= -7373;
-  z2 *= -20995;
-  z3 = z3 * -16069 + z5;
-  z4 = z4 * -3196 + z5;
-  d7 = (t4 + z1 + z3 + kRound) >> kShift;
-  d5 = (t5 + z2 + z4 + kRound) >> kShift;
-  d3 = (t6 + z2 + z3 + kRound) >> kShift;
-  d1 = (t7 + z1 + z4 + kRound) >> kShift;
+  jpeg_dct_odd(t4, t5, t6, t7);
+  d7 = (t4 + kRound) >> kShift;
+  d5 = (t5 + kRound) >> kShift;
+  d3 = (t6 + kRound) >> kShift;
+  d1 = (t7 + kRound) >> kShift;
 }
 
-// whether block k of an MCU (scan order: hs * vs luma blocks row by row, then Cb, Cr) is a dummy block of image h x w
+// Block k of an MCU in scan order - nl = hs * vs luma blocks row by row, then Cb, Cr: its component, and for a luma block
+// its place (by, bx) among the MCU's luma blocks.
+__device__ __forceinline__ int jpeg_block_component(int k, int nl) { return k < nl ? 0 : k - nl + 1; }
+
+__device__ __forceinline__ void jpeg_luma_block_at(int k, int hs, int &by, int &bx) {  // k < nl
+  by = k / hs;
+  bx = k - by * hs;
+}
+
+// coefficient j (0..7) of the eight int16 a 16-byte vector of a block holds
+__device__ __forceinline__ int jpeg_coef(const CodecVec16 &q, int j) {
+  const uint32_t wv[4] = {q.x, q.y, q.z, q.w};
+  return (int)(int16_t)((wv[j >> 1] >> (16 * (j & 1))) & 0xFFFFu);
+}
+
+// whether block k of an MCU is a dummy block of image h x w
 __device__ __forceinline__ bool jpeg_is_dummy(int k, int hs, int vs, int mcu, int row, int h, int w) {
   if (k >= hs * vs) return false;
-  const int by = k / hs, bx = k - by * hs;
+  int by, bx;
+  jpeg_luma_block_at(k, hs, by, bx);
   return (mcu * hs + bx) * 8 >= w || (row * vs + by) * 8 >= h;
 }
 
@@ -206,7 +233,8 @@ __global__ __launch_bounds__(kJpegThreads) void jpeg_blocks(int16_t *__restrict_
     const uint8_t *src;
     int pitch;
     if (k < nl) {
-      const int by = k / hs, bx = k - by * hs;
+      int by, bx;
+      jpeg_luma_block_at(k, hs, by, bx);
       src = Y + by * 8 * yw + (mcu * hs + bx) * 8;
       pitch = yw;
     } else {
@@ -257,51 +285,24 @@ __global__ __launch_bounds__(kJpegThreads) void jpeg_blocks(int16_t *__restrict_
     pk[0] = (uint32_t)dc & 0xFFFFu;
   }
   const long long blk = ((long long)img * rows + row) * ((long long)mcus * nb) + (long long)(m0 + mcu) * nb + k;
-  JpegVec16 *dst = reinterpret_cast<JpegVec16 *>(coefs + blk * 64);
+  CodecVec16 *dst = reinterpret_cast<CodecVec16 *>(coefs + blk * 64);
 #pragma unroll
-  for (int i = 0; i < 8; ++i) dst[i] = JpegVec16{pk[4 * i], pk[4 * i + 1], pk[4 * i + 2], pk[4 * i + 3]};
+  for (int i = 0; i < 8; ++i) dst[i] = CodecVec16{pk[4 * i], pk[4 * i + 1], pk[4 * i + 2], pk[4 * i + 3]};
 }
 
-// bits appended MSB-first at a bit offset of a zeroed word array (stream bit p is bit 31 - p % 32 of word p / 32); words
-// shared with a neighbour are completed by atomic add
-struct JpegBits {
-  uint32_t *w;
-  uint64_t acc;
-  int n, pos;
-  __device__ __forceinline__ void init(uint32_t *words, uint32_t bit_offset) {
-    w = words;
-    pos = (int)(bit_offset >> 5);
-    n = (int)(bit_offset & 31u);
-    acc = 0;
-  }
-  __device__ __forceinline__ void put(uint32_t v, int nb) {  // 0 < nb <= 32, v < 2^nb
-    acc |= (uint64_t)v << (64 - n - nb);
-    n += nb;
-    if (n >= 32) {
-      atomicAdd(&w[pos++], (uint32_t)(acc >> 32));
-      acc <<= 32;
-      n -= 32;
-    }
-  }
-  __device__ __forceinline__ void flush() {
-    if (n > 0) atomicAdd(&w[pos], (uint32_t)(acc >> 32));
-    n = 0;
-    acc = 0;
-  }
-};
+using JpegBits = CodecBits<true>;  // the entropy-coded segment packs bits MSB first
 
 // The code of one block (64 int16 in zig-zag order, 16-byte aligned) with DC predictor `pred`: put(bits, count) for the DC
 // symbol, every AC (run, size) symbol with its value bits, ZRL for runs above 15, EOB unless coefficient 63 is non-zero.
 template <class Put>
 __device__ __forceinline__ void jpeg_block_code(const int16_t *blk, int pred, const uint32_t *dct, const uint32_t *act, Put &&put) {
-  const JpegVec16 *v = reinterpret_cast<const JpegVec16 *>(blk);
+  const CodecVec16 *v = reinterpret_cast<const CodecVec16 *>(blk);
   int run = 0;
   for (int gI = 0; gI < 8; ++gI) {
-    const JpegVec16 q = v[gI];
-    const uint32_t wv[4] = {q.x, q.y, q.z, q.w};
+    const CodecVec16 q = v[gI];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const int c = (int)(int16_t)((wv[j >> 1] >> (16 * (j & 1))) & 0xFFFFu);
+      const int c = jpeg_coef(q, j);
       if (gI == 0 && j == 0) {
         const int diff = c - pred;
         const uint32_t a = (uint32_t)(diff < 0 ? -diff : diff);
@@ -331,34 +332,22 @@ __device__ __forceinline__ void jpeg_block_code(const int16_t *blk, int pred, co
   if (run) put(act[0] & 0xFFFFu, (int)(act[0] >> 16));
 }
 
-// ALL threads (contains barriers): inclusive sum of v over the workgroup in thread order; buf holds 2 * kJpegThreads words
-__device__ __forceinline__ uint32_t jpeg_scan(uint32_t *buf, int tid, uint32_t v, uint32_t &total) {
-  uint32_t *src = buf, *dst = buf + kJpegThreads;
-  __syncthreads();  // the readers of an earlier scan are done
-  src[tid] = v;
-  __syncthreads();
-  for (int d = 1; d < kJpegThreads; d <<= 1) {
-    dst[tid] = src[tid] + (tid >= d ? src[tid - d] : 0u);
-    __syncthreads();
-    uint32_t *t = src;
-    src = dst;
-    dst = t;
-  }
-  total = src[kJpegThreads - 1];
-  return src[tid];
-}
-
 __device__ __forceinline__ uint32_t jpeg_stream_byte(const uint32_t *words, uint32_t p) { return (words[p >> 2] >> (24u - 8u * (p & 3u))) & 255u; }
 
+// jpeg_entropy's dynamic LDS in words: bit buffer [nwords] | code tables | scan | carry.  The bit buffer takes the bits of a
+// chunk of `blocks` blocks, a carried byte, the padding, and is rounded to whole 16 bytes.
+constexpr int kJpegTabWords = 32 + 2 * 256;  // DC codes [2][12] padded to 32, AC codes [2][256]
+constexpr int jpeg_entropy_words(int blocks) { return ((blocks * kJpegBlockBits + 8 + 31) / 32 + 1 + 3) / 4 * 4; }
+constexpr int jpeg_entropy_lds_words(int nwords) { return nwords + kJpegTabWords + 2 * kJpegThreads + 4; }
+
 // One restart interval (MCU row) -> its byte-stuffed entropy-coded bytes in its workspace slot, the length in meta.
-// Dynamic LDS: bit buffer [nwords] | code tables [544] | scan [512] | carry [4].
 __global__ __launch_bounds__(kJpegThreads) void jpeg_entropy(uint8_t *__restrict__ slots, uint32_t *__restrict__ meta,
                                                              const int16_t *__restrict__ coefs, int hs, int vs, int nb, int mcus,
                                                              int tile, long long slot_bytes, int nwords, JpegCodes C) {
   HF_DYN_LDS;
   uint32_t *words = reinterpret_cast<uint32_t *>(hf_dyn_lds);
   uint32_t *tab = words + nwords;
-  uint32_t *scan = tab + 544;
+  uint32_t *scan = tab + kJpegTabWords;
   uint32_t *carry = scan + 2 * kJpegThreads;  // partial byte, its bit count, bytes written so far
   const int tid = (int)threadIdx.x;
   const int row = (int)blockIdx.x, rows = (int)gridDim.x, img = (int)blockIdx.y;
@@ -389,7 +378,7 @@ __global__ __launch_bounds__(kJpegThreads) void jpeg_entropy(uint8_t *__restrict
     uint32_t bits = 0;
     if (active) jpeg_block_code(rc + blk * 64, pred, dct, act, [&](uint32_t, int n) { bits += (uint32_t)n; });
     uint32_t total;
-    const uint32_t incl = jpeg_scan(scan, tid, bits, total);
+    const uint32_t incl = codec_scan<kJpegThreads>(scan, tid, bits, total);
     const int nzero = (int)((cbits + total + 8u) >> 5) + 1;  // the words this chunk's bits and padding reach, at most nwords
     for (int i = tid; i < nzero && i < nwords; i += kJpegThreads) words[i] = 0;
     __syncthreads();
@@ -415,7 +404,7 @@ __global__ __launch_bounds__(kJpegThreads) void jpeg_entropy(uint8_t *__restrict
     uint32_t ff = 0;
     for (uint32_t p = a; p < b; ++p) ff += jpeg_stream_byte(words, p) == 255u ? 1u : 0u;
     uint32_t nff;
-    const uint32_t ffi = jpeg_scan(scan, tid, ff, nff);
+    const uint32_t ffi = codec_scan<kJpegThreads>(scan, tid, ff, nff);
     uint8_t *dst = slot + out_off + a + (ffi - ff);
     for (uint32_t p = a; p < b; ++p) {
       const uint32_t v = jpeg_stream_byte(words, p);
@@ -441,32 +430,14 @@ __global__ __launch_bounds__(kJpegThreads) void jpeg_assemble(uint8_t *__restric
   const int tid = (int)threadIdx.x;
   const int row = (int)blockIdx.x, rows = (int)gridDim.x, img = (int)blockIdx.y;
   const uint32_t *mimg = meta + (long long)img * rows;
-  if (tid == 0) sum[0] = 0;
-  __syncthreads();
-  uint32_t part = 0;
-  for (int s = tid; s < row; s += kJpegThreads) part += mimg[s] + 2u;  // an interval and the marker behind it
-  if (part) atomicAdd(&sum[0], part);
+  codec_sum_before<kJpegThreads>(sum, row, tid, [&](int s) { return mimg[s] + 2u; });  // an interval and the marker behind it
   __syncthreads();
   const uint32_t off = (uint32_t)H.n + sum[0];
   const uint32_t n = mimg[row];
   const uint8_t *src = slots + ((long long)img * rows + row) * slot_bytes;
-  const uint32_t *srcw = reinterpret_cast<const uint32_t *>(src);
   uint8_t *o = out + (long long)img * out_stride;
   uint8_t *dst = o + off;
-
-  uint32_t head = (uint32_t)((4u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 3u)) & 3u);
-  if (head > n) head = n;
-  const uint32_t nw = (n - head) >> 2;
-  if ((uint32_t)tid < head) dst[tid] = src[tid];
-  uint32_t *dstw = reinterpret_cast<uint32_t *>(dst + head);
-  const uint32_t sh = (head & 3u) * 8u;
-  for (uint32_t j = (uint32_t)tid; j < nw; j += kJpegThreads) {
-    const uint32_t wi = (head + 4u * j) >> 2;
-    const uint32_t w0 = srcw[wi];
-    dstw[j] = sh ? (w0 >> sh) | (srcw[wi + 1] << (32u - sh)) : w0;  // the slot has 16 bytes behind its longest interval
-  }
-  const uint32_t done = head + 4u * nw;
-  if ((uint32_t)tid < n - done) dst[done + tid] = src[done + tid];
+  codec_copy_slot<kJpegThreads>(dst, src, n, tid);
   if (tid == 0) {
     dst[n] = 0xFF;
     if (row + 1 < rows) {
@@ -480,21 +451,34 @@ __global__ __launch_bounds__(kJpegThreads) void jpeg_assemble(uint8_t *__restric
     for (int i = tid; i < H.n; i += kJpegThreads) o[i] = H.b[i];
 }
 
-struct JpegShape {
-  int nc, hs, vs, nb, mcus, rows, tile, header;
+// The MCU geometry that encoder and decoder derive from a frame: nl luma blocks and nb blocks per MCU, MCUs per MCU row, MCU rows
+struct JpegMcus {
+  int nc, hs, vs, nl, nb, mcus, rows;
+};
+
+// false: a dimension outside 1..65535, components other than 1 / 3, luma sampling other than 1x1 or, with three components,
+// 2x1 and 2x2 (the chroma components are 1x1)
+inline bool jpeg_mcus(int h, int w, int components, int hs, int vs, JpegMcus &m) {
+  if (h <= 0 || w <= 0 || h > 65535 || w > 65535 || (components != 1 && components != 3)) return false;
+  if (!((hs == 1 && vs == 1) || (components == 3 && hs == 2 && (vs == 1 || vs == 2)))) return false;
+  m.nc = components, m.hs = hs, m.vs = vs;
+  m.nl = hs * vs;
+  m.nb = m.nl + (components == 3 ? 2 : 0);
+  m.mcus = (w + 8 * hs - 1) / (8 * hs);
+  m.rows = (h + 8 * vs - 1) / (8 * vs);
+  return true;
+}
+
+struct JpegShape : JpegMcus {
+  int tile, header;
   long long row_blocks, slot, bound;
 };
 
-// false: a shape the encoder does not take (channels other than 1 / 3, a dimension outside 1..65535, subsampling outside
-// 0..2, a file of 2 GiB or more)
+// false: a shape the encoder does not take (what jpeg_mcus refuses, subsampling outside 0..2, a file of 2 GiB or more)
 inline bool jpeg_shape(int h, int w, int channels, int subsampling, JpegShape &s) {
-  if (h <= 0 || w <= 0 || h > 65535 || w > 65535 || (channels != 1 && channels != 3) || subsampling < 0 || subsampling > 2) return false;
-  s.nc = channels;
-  s.hs = (channels == 3 && subsampling > 0) ? 2 : 1;
-  s.vs = (channels == 3 && subsampling == 2) ? 2 : 1;
-  s.nb = s.hs * s.vs + (channels == 3 ? 2 : 0);
-  s.mcus = (w + 8 * s.hs - 1) / (8 * s.hs);
-  s.rows = (h + 8 * s.vs - 1) / (8 * s.vs);
+  if (subsampling < 0 || subsampling > 2) return false;
+  const int hs = (channels == 3 && subsampling > 0) ? 2 : 1, vs = (channels == 3 && subsampling == 2) ? 2 : 1;
+  if (!jpeg_mcus(h, w, channels, hs, vs, s)) return false;
   s.tile = kJpegThreads / s.nb;
   s.row_blocks = (long long)s.mcus * s.nb;
   // SOI 2, APP0 18, DQT 69 each, SOF0 10 + 3 nc, DHT 33 + 183 per table pair, DRI 6, SOS 8 + 2 nc
@@ -506,8 +490,6 @@ inline bool jpeg_shape(int h, int w, int channels, int subsampling, JpegShape &s
 }
 
 inline long long jpeg_meta_bytes(int batch, const JpegShape &s) { return ((long long)batch * s.rows * 4 + 15) / 16 * 16; }
-
-inline int jpeg_entropy_words(const JpegShape &s) { return ((s.tile * s.nb * kJpegBlockBits + 8 + 31) / 32 + 1 + 3) / 4 * 4; }
 
 inline void jpeg_put_segment(JpegHeader &H, int marker, int body) {
   H.b[H.n++] = 0xFF;
@@ -622,9 +604,9 @@ extern "C" int hf_jpeg_encode_u8(unsigned char *out, long long out_stride, long 
   uint8_t *slots = reinterpret_cast<uint8_t *>(coefs) + (long long)batch * s.rows * s.row_blocks * 128;
   const int tiles = (s.mcus + s.tile - 1) / s.tile;
   const size_t lds_blocks = (size_t)s.tile * 64 * s.nb + kJpegThreads * 4;
-  const int nwords = jpeg_entropy_words(s);
-  const size_t lds_entropy = ((size_t)nwords + 544 + 2 * kJpegThreads + 4) * 4;
-  static_assert(((kJpegThreads * kJpegBlockBits + 8 + 31) / 32 + 4 + 544 + 2 * kJpegThreads + 4) * 4 <= 65536,
+  const int nwords = jpeg_entropy_words(s.tile * s.nb);
+  const size_t lds_entropy = (size_t)jpeg_entropy_lds_words(nwords) * 4;
+  static_assert(jpeg_entropy_lds_words(jpeg_entropy_words(kJpegThreads)) * 4 <= 65536,
                 "a chunk's LDS stays inside the 64 KiB a kernel gets without opting in");
   static_assert(sizeof(JpegCodes) + sizeof(JpegHeader) + sizeof(JpegQuant) < 4096, "tables passed by value: the kernel argument limit");
   hipStream_t st = (hipStream_t)stream;

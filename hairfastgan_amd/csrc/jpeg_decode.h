@@ -37,6 +37,8 @@
 // interval's block count and a zig-zag index below 64, every loop is bounded by the shape or the scan length.  A code that is
 // not in the table, a block of more than 64 coefficients, a DC size above 11, a wrong or missing marker and a scan that ends
 // early set status[2 b] (the largest code wins); status[2 b + 1] is the largest number of synchronisation passes of a window.
+// From jpeg.h: kJpegNatural, jpeg_dct_odd, jpeg_mcus, jpeg_block_component / jpeg_luma_block_at, jpeg_coef; through it from
+// codec_common.h: CodecVec16, codec_scan (every scan below), codec_sum_before (jpegd_marker_place).
 #pragma once
 #include <cstdint>
 
@@ -53,8 +55,8 @@ constexpr int kJdChunk = 16384;      // bytes of the scan per workgroup of the m
 constexpr uint32_t kJdDead = 0xFFFFFFFFu;
 enum { JD_OK = 0, JD_TRUNCATED = 1, JD_MARKER = 2, JD_COEFS = 3, JD_CODE = 4, JD_DC = 5 };
 
-struct JdGeom {
-  int h, w, nc, hs, vs, nb, nl, mcus_x, mcus_y, ri, n_int;  // ri: MCUs per interval (all of them without DRI)
+struct JdGeom : JpegMcus {
+  int ri, n_int;  // ri: MCUs per interval (all of them without DRI)
   long long total_mcus, total_blocks, yw, yh, cw, ch;
   long long coef_bytes, plane_bytes, bounds_bytes, counts_bytes;
   int nchunks;
@@ -69,12 +71,12 @@ __device__ __forceinline__ void jd_scan_range(const long long *offsets, int b, l
   len = (uint32_t)((e - s) > 0x7fffffffLL ? 0x7fffffffLL : (e - s));
 }
 
-__global__ __launch_bounds__(kJdThreads) void jpegd_clear(JpegVec16 *__restrict__ coefs, long long n16, int *__restrict__ status,
+__global__ __launch_bounds__(kJdThreads) void jpegd_clear(CodecVec16 *__restrict__ coefs, long long n16, int *__restrict__ status,
                                                           uint32_t *__restrict__ bounds, const long long *__restrict__ offsets,
                                                           long long scans_bytes, int batch, int n_int) {
   const long long stride = (long long)gridDim.x * kJdThreads;
   const long long t0 = (long long)blockIdx.x * kJdThreads + threadIdx.x;
-  for (long long i = t0; i < n16; i += stride) coefs[i] = JpegVec16{0u, 0u, 0u, 0u};
+  for (long long i = t0; i < n16; i += stride) coefs[i] = CodecVec16{0u, 0u, 0u, 0u};
   for (long long i = t0; i < 2ll * batch; i += stride) status[i] = 0;
   for (long long i = t0; i < (long long)batch * n_int; i += stride) {
     long long s;
@@ -121,17 +123,13 @@ __global__ __launch_bounds__(kJdThreads) void jpegd_marker_place(uint32_t *__res
   uint32_t len;
   jd_scan_range(offsets, b, scans_bytes, start, len);
   const uint8_t *g = scans + start;
-  if (tid == 0) sum[0] = 0;
-  __syncthreads();
-  uint32_t part = 0;
-  for (int i = tid; i < c; i += kJdThreads) part += counts[(long long)b * gridDim.x + i];
-  if (part) atomicAdd(&sum[0], part);
+  codec_sum_before<kJdThreads>(sum, c, tid, [&](int i) { return counts[(long long)b * gridDim.x + i]; });
   const uint64_t a = (uint64_t)c * kJdChunk + (uint64_t)tid * (kJdChunk / kJdThreads);
   uint32_t n = 0;
   for (int i = 0; i < kJdChunk / kJdThreads; ++i)
     if (a + i < len && jd_marker_at(g, (uint32_t)(a + i), len)) ++n;
   uint32_t total;
-  const uint32_t incl = jpeg_scan(scan, tid, n, total);  // its barriers also publish sum[0]
+  const uint32_t incl = codec_scan<kJdThreads>(scan, tid, n, total);  // its barriers also publish sum[0]: codec_sum_before leaves that to its caller
   uint64_t j = (uint64_t)sum[0] + incl - n;
   if (n == 0) return;
   for (int i = 0; i < kJdChunk / kJdThreads; ++i) {
@@ -173,8 +171,8 @@ __device__ __forceinline__ uint32_t jd_decode_sub(const uint8_t *buf, uint32_t &
   int err = 0;
   while (pos < end_bits) {
     if (WRITE && blk >= expected) break;
-    const int comp = k < nl ? 0 : k - nl + 1;
-    const int t = (z == 0 ? 0 : 3) + comp;
+    const int comp = k < nl ? 0 : k - nl + 1;  // jpeg_block_component written out: called here, the compiler schedules
+    const int t = (z == 0 ? 0 : 3) + comp;     // jpegd_entropy differently; so its machine code stays what it was
     const uint32_t v = jd_peek(buf, pos);
     uint32_t e = T.look[t * 256 + (v >> 24)];
     int len = (int)(e >> 8), sym = (int)(e & 255u);
@@ -275,6 +273,12 @@ __device__ __forceinline__ uint32_t jd_unstuff(const uint8_t *g, uint32_t a, uin
 
 // Dynamic LDS: bytes [threads * sub + 32] | look [6 * 256] u16 | maxcode [6 * 17] | valoff [6 * 17] | vals [6 * 256] |
 //              entry pos, entry kz, exit pos, exit kz, exit blocks [5 * threads] | scan [2 * threads] | misc [16]
+constexpr int kJdLaneArrays = 5, kJdMiscWords = 16;
+constexpr size_t jd_entropy_lds(int sub) {
+  return (size_t)kJdThreads * sub + 32 + 6 * 256 * 2 + 2 * 6 * 17 * 4 + 6 * 256 + (kJdLaneArrays + 2) * kJdThreads * 4 + kJdMiscWords * 4;
+}
+static_assert(jd_entropy_lds(kJdSubMax) <= 65536, "the entropy kernel's LDS stays inside the 64 KiB a kernel gets without opting in");
+
 __global__ __launch_bounds__(kJdThreads) void jpegd_entropy(int16_t *__restrict__ coefs, int *__restrict__ status,
                                                             const uint8_t *__restrict__ scans, const long long *__restrict__ offsets,
                                                             long long scans_bytes, const uint8_t *__restrict__ tables,
@@ -290,7 +294,7 @@ __global__ __launch_bounds__(kJdThreads) void jpegd_entropy(int16_t *__restrict_
   uint8_t *vals = reinterpret_cast<uint8_t *>(valoff + 6 * 17);
   uint32_t *ent_pos = reinterpret_cast<uint32_t *>(vals + 6 * 256);
   uint32_t *ent_kz = ent_pos + kJdThreads, *ex_pos = ent_kz + kJdThreads, *ex_kz = ex_pos + kJdThreads, *ex_n = ex_kz + kJdThreads;
-  uint32_t *scan = ex_n + kJdThreads;
+  uint32_t *scan = ent_pos + kJdLaneArrays * kJdThreads;
   uint32_t *misc = scan + 2 * kJdThreads;  // 0, 1: changed flags; 2: inverted cut; 3: end position of the last block
   const uint8_t *tab = tables + (long long)img * kJdTableBytes + kJdHuffOffset;
   int *st = status + 2 * img;
@@ -363,7 +367,7 @@ __global__ __launch_bounds__(kJdThreads) void jpegd_entropy(int16_t *__restrict_
     const uint32_t cut = 0xFFFFFFFFu - misc[2];  // 0xFFFFFFFF: none
     if (a > cut) kept = 0;
     uint32_t total_kept;
-    const uint32_t incl = jpeg_scan(scan, tid, kept, total_kept);
+    const uint32_t incl = codec_scan<kJdThreads>(scan, tid, kept, total_kept);
     if (kept) {
       uint32_t dummy;
       jd_unstuff<true>(g, a, b, ilen, buf + carry_n + incl - kept, dummy);
@@ -415,7 +419,7 @@ __global__ __launch_bounds__(kJdThreads) void jpegd_entropy(int16_t *__restrict_
     max_passes = passes > max_passes ? passes : max_passes;
     // ---- 4. block indices, then the coefficients ----
     uint32_t nblocks;
-    const uint32_t bincl = jpeg_scan(scan, tid, lane ? ex_n[tid] : 0u, nblocks);
+    const uint32_t bincl = codec_scan<kJdThreads>(scan, tid, lane ? ex_n[tid] : 0u, nblocks);
     if (lane) {
       uint32_t p = ent_pos[tid], kz = ent_kz[tid];
       jd_decode_sub<true>(buf, p, kz, my_end, T, nb, nl, ic, done + (long long)(bincl - ex_n[tid]), expected, st, &misc[3]);
@@ -460,7 +464,7 @@ __global__ __launch_bounds__(kJdThreads) void jpegd_entropy(int16_t *__restrict_
     }
     for (int c = 0; c < nc; ++c) {
       uint32_t total;
-      const uint32_t inc = jpeg_scan(scan, tid, sum[c], total);
+      const uint32_t inc = codec_scan<kJdThreads>(scan, tid, sum[c], total);
       uint32_t v = run[c] + inc - sum[c];
       run[c] += total;
       if (!active) continue;
@@ -481,26 +485,12 @@ __global__ __launch_bounds__(kJdThreads) void jpegd_entropy(int16_t *__restrict_
 template <int SHIFT>
 __device__ __forceinline__ void jd_idct8(int &d0, int &d1, int &d2, int &d3, int &d4, int &d5, int &d6, int &d7) {
   constexpr int kRound = 1 << (SHIFT - 1);
-  int z1 = (d2 + d6) * 4433;
+  const int z1 = (d2 + d6) * 4433;
   const int tmp2 = z1 - d6 * 15137, tmp3 = z1 + d2 * 6270;
   const int tmp0 = (d0 + d4) * 8192, tmp1 = (d0 - d4) * 8192;
   const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
   int t0 = d7, t1 = d5, t2 = d3, t3 = d1;
-  z1 = t0 + t3;
-  int z2 = t1 + t2, z3 = t0 + t2, z4 = t1 + t3;
-  const int z5 = (z3 + z4) * 9633;
-  t0 *= 2446;
-  t1 *= 16819;
-  t2 *= 25172;
-  t3 *= 12299;
-  z1 *= -7373;
-  z2 *= -20995;
-  z3 = z3 * -16069 + z5;
-  z4 = z4 * -3196 + z5;
-  t0 += z1 + z3;
-  t1 += z2 + z4;
-  t2 += z2 + z3;
-  t3 += z1 + z4;
+  jpeg_dct_odd(t0, t1, t2, t3);
   d0 = (tmp10 + t3 + kRound) >> SHIFT;
   d7 = (tmp10 - t3 + kRound) >> SHIFT;
   d1 = (tmp11 + t2 + kRound) >> SHIFT;
@@ -526,28 +516,28 @@ __global__ __launch_bounds__(kJdThreads) void jpegd_blocks(uint8_t *__restrict__
   const long long mcu = blk / nb;
   const int k = (int)(blk - mcu * nb);
   const long long my = mcu / mcus_x, mx = mcu - my * mcus_x;
-  const int comp = k < nl ? 0 : k - nl + 1;
+  const int comp = jpeg_block_component(k, nl);
   uint8_t *dst = planes + (long long)img * image_planes;
   long long pitch;
   if (k < nl) {
-    const int by = k / hs, bx = k - by * hs;
+    int by, bx;
+    jpeg_luma_block_at(k, hs, by, bx);
     pitch = yw;
     dst += ((my * (nl / hs) + by) * 8) * yw + (mx * hs + bx) * 8;
   } else {
     pitch = cw;
     dst += ysize + (long long)(comp - 1) * csize + (my * 8) * cw + mx * 8;
   }
-  const JpegVec16 *src = reinterpret_cast<const JpegVec16 *>(coefs + ((long long)img * total_blocks + blk) * 64);
+  const CodecVec16 *src = reinterpret_cast<const CodecVec16 *>(coefs + ((long long)img * total_blocks + blk) * 64);
   const uint16_t *qc = q + comp * 64;
   int d[64];
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
-    const JpegVec16 v = src[i];
-    const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
+    const CodecVec16 v = src[i];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int n = kJpegNatural[i * 8 + j];
-      d[n] = (int)(int16_t)((wv[j >> 1] >> (16 * (j & 1))) & 0xFFFFu) * (int)qc[n];
+      d[n] = jpeg_coef(v, j) * (int)qc[n];
     }
   }
 #pragma unroll
@@ -620,28 +610,17 @@ __global__ __launch_bounds__(kJdThreads) void jpegd_pixels(uint8_t *__restrict__
 
 // false: a geometry the decoder does not take
 inline bool jd_geometry(int batch, int h, int w, int components, int hs, int vs, int restart_interval, long long max_scan_bytes, JdGeom &g) {
-  if (batch <= 0 || batch > 65535 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || restart_interval < 0 || restart_interval > 65535) return false;
+  if (batch <= 0 || batch > 65535 || restart_interval < 0 || restart_interval > 65535) return false;
   if (max_scan_bytes < 0 || max_scan_bytes > 0x7fffffffLL) return false;
-  if (components == 1) {
-    if (hs != 1 || vs != 1) return false;
-  } else if (components == 3) {
-    if (!((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2))) return false;
-  } else {
-    return false;
-  }
-  g.h = h, g.w = w, g.nc = components, g.hs = hs, g.vs = vs;
-  g.nl = hs * vs;
-  g.nb = g.nl + (components == 3 ? 2 : 0);
-  g.mcus_x = (w + 8 * hs - 1) / (8 * hs);
-  g.mcus_y = (h + 8 * vs - 1) / (8 * vs);
-  g.total_mcus = (long long)g.mcus_x * g.mcus_y;
+  if (!jpeg_mcus(h, w, components, hs, vs, g)) return false;
+  g.total_mcus = (long long)g.mcus * g.rows;
   g.total_blocks = g.total_mcus * g.nb;
   const long long per = restart_interval ? restart_interval : g.total_mcus;
   const long long n_int = (g.total_mcus + per - 1) / per;
   if (per > 0x7fffffffLL || n_int > 0x7fffffffLL) return false;
   g.ri = (int)per, g.n_int = (int)n_int;
-  g.yw = (long long)g.mcus_x * hs * 8, g.yh = (long long)g.mcus_y * vs * 8;
-  g.cw = (long long)g.mcus_x * 8, g.ch = (long long)g.mcus_y * 8;
+  g.yw = (long long)g.mcus * hs * 8, g.yh = (long long)g.rows * vs * 8;
+  g.cw = (long long)g.mcus * 8, g.ch = (long long)g.rows * 8;
   g.coef_bytes = (long long)batch * g.total_blocks * 128;
   g.plane_bytes = (g.yw * g.yh + (components == 3 ? 2 * g.cw * g.ch : 0) + 15) / 16 * 16;
   g.bounds_bytes = ((long long)batch * g.n_int * 4 + 15) / 16 * 16;
@@ -649,10 +628,6 @@ inline bool jd_geometry(int batch, int h, int w, int components, int hs, int vs,
   g.nchunks = g.nchunks < 1 ? 1 : g.nchunks;
   g.counts_bytes = restart_interval ? ((long long)batch * g.nchunks * 4 + 15) / 16 * 16 : 0;
   return g.coef_bytes + (long long)batch * g.plane_bytes < (1ll << 40);
-}
-
-inline size_t jd_entropy_lds(int sub) {
-  return (size_t)kJdThreads * sub + 32 + 6 * 256 * 2 + 2 * 6 * 17 * 4 + 6 * 256 + 5 * kJdThreads * 4 + 2 * kJdThreads * 4 + 16 * 4;
 }
 
 }  // namespace
@@ -679,8 +654,6 @@ extern "C" int hf_jpeg_decode_u8(unsigned char *out, float *out_f32, int *status
       (reinterpret_cast<uintptr_t>(out_f32) & 3u) != 0)
     return HF_E_INVALID;
   if (workspace_bytes < hf_jpeg_decode_workspace_bytes(batch, h, w, components, hs, vs, restart_interval, max_scan_bytes)) return HF_E_WORKSPACE;
-  static_assert((size_t)kJdThreads * kJdSubMax + 32 + 6 * 256 * 2 + 2 * 6 * 17 * 4 + 6 * 256 + 7 * kJdThreads * 4 + 64 <= 65536,
-                "the entropy kernel's LDS stays inside the 64 KiB a kernel gets without opting in");
   uint8_t *ws = static_cast<uint8_t *>(workspace);
   int16_t *coefs = reinterpret_cast<int16_t *>(ws);
   uint8_t *planes = ws + g.coef_bytes;
@@ -691,7 +664,7 @@ extern "C" int hf_jpeg_decode_u8(unsigned char *out, float *out_f32, int *status
   const long long clear_items = n16 > (long long)batch * g.n_int ? n16 : (long long)batch * g.n_int;
   long long cg = (clear_items + kJdThreads - 1) / kJdThreads;
   cg = cg > 16384 ? 16384 : (cg < 1 ? 1 : cg);
-  hipLaunchKernelGGL(jpegd_clear, dim3((unsigned)cg), dim3(kJdThreads), 0, st, reinterpret_cast<JpegVec16 *>(coefs), n16, status, bounds,
+  hipLaunchKernelGGL(jpegd_clear, dim3((unsigned)cg), dim3(kJdThreads), 0, st, reinterpret_cast<CodecVec16 *>(coefs), n16, status, bounds,
                      scan_offsets, scans_bytes, batch, g.n_int);
   if (hf_launch_status() != HF_OK) return HF_E_LAUNCH;
   if (restart_interval) {
@@ -706,7 +679,7 @@ extern "C" int hf_jpeg_decode_u8(unsigned char *out, float *out_f32, int *status
   if (hf_launch_status() != HF_OK) return HF_E_LAUNCH;
   const long long ysize = g.yw * g.yh, csize = g.cw * g.ch;
   hipLaunchKernelGGL(jpegd_blocks, dim3((unsigned)((g.total_blocks + kJdThreads - 1) / kJdThreads), batch), dim3(kJdThreads), 384, st, planes,
-                     coefs, tables, g.total_blocks, g.nb, g.nl, g.hs, g.mcus_x, g.yw, ysize, g.cw, csize, g.plane_bytes);
+                     coefs, tables, g.total_blocks, g.nb, g.nl, g.hs, g.mcus, g.yw, ysize, g.cw, csize, g.plane_bytes);
   if (hf_launch_status() != HF_OK) return HF_E_LAUNCH;
   const long long npix = (long long)h * w;
   hipLaunchKernelGGL(jpegd_pixels, dim3((unsigned)((npix + kJdThreads - 1) / kJdThreads), batch), dim3(kJdThreads), 0, st, out, out_f32, planes,

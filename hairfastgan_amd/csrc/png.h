@@ -32,9 +32,12 @@
 //   lengths, checksums, IEND and sizes[b].
 // Every loop is bounded by the shape (the Kraft repair by the symbol count); passes that depend on each other are separate
 // launches; the bytes of image b depend on that image, the shape and the filter mode only.
+// The 16-byte vector, the bit packer (PngBits is its LSB-first form), the sum of the sizes before a segment and the copy of
+// a slot to the file are codec_common.h's, shared with jpeg.h.
 #pragma once
 #include <cstdint>
 
+#include "codec_common.h"
 #include "hf_common.h"
 
 namespace {
@@ -48,10 +51,6 @@ constexpr int kPngTailBytes = 25;    // final block 5, Adler 4, IDAT CRC 4, IEND
 constexpr int kPngMetaWords = 8;     // per segment: size, adler a, adler b, crc, offset
 constexpr uint32_t kCrcPoly = 0xEDB88320u;
 constexpr uint32_t kAdlerMod = 65521u;
-
-struct alignas(16) PngVec16 {
-  uint32_t x, y, z, w;
-};
 
 // order in which the code-length code's lengths are sent (RFC 1951 3.2.7)
 static __device__ const unsigned char kPngClOrder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
@@ -93,32 +92,7 @@ __device__ __forceinline__ uint32_t png_filter(uint32_t type, uint32_t x, uint32
   return (x - pred) & 255u;
 }
 
-// bits appended LSB-first at a bit offset of a zeroed word array; words shared with a neighbour are completed by atomic add
-struct PngBits {
-  uint32_t *w;
-  uint64_t acc;
-  int n, pos;
-  __device__ __forceinline__ void init(uint32_t *words, uint32_t bit_offset) {
-    w = words;
-    pos = (int)(bit_offset >> 5);
-    n = (int)(bit_offset & 31u);
-    acc = 0;
-  }
-  __device__ __forceinline__ void put(uint32_t v, int nb) {  // nb <= 32
-    acc |= (uint64_t)v << n;
-    n += nb;
-    if (n >= 32) {
-      atomicAdd(&w[pos++], (uint32_t)acc);
-      acc >>= 32;
-      n -= 32;
-    }
-  }
-  __device__ __forceinline__ void flush() {
-    if (n > 0) atomicAdd(&w[pos], (uint32_t)acc);
-    n = 0;
-    acc = 0;
-  }
-};
+using PngBits = CodecBits<false>;  // deflate packs bits LSB first
 
 // match length 3..258 -> length code index (symbol 257 + index), number and value of the extra bits
 __device__ __forceinline__ void png_length_code(int m, int &idx, int &eb, uint32_t &ev) {
@@ -377,6 +351,11 @@ __device__ __forceinline__ uint32_t png_crc_xpow8(uint32_t nbytes) {  // x^(8 * 
   return result;
 }
 
+__device__ __forceinline__ int png_put_be32(uint8_t *stage, int n, uint32_t v) {  // -> the position behind the value
+  for (int i = 0; i < 4; ++i) stage[n + i] = (uint8_t)(v >> (24 - 8 * i));
+  return n + 4;
+}
+
 __device__ __forceinline__ uint32_t png_crc_byte(uint32_t c, uint32_t byte) {  // table-free, for the few header bytes
   c ^= byte;
   for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ kCrcPoly : c >> 1;
@@ -420,7 +399,7 @@ __global__ __launch_bounds__(kPngThreads) void png_segment(uint8_t *__restrict__
     const int nvec = (nraw - head) >> 4;
     if (tid < head) raw[tid] = g[tid];
     for (int j = tid; j < nvec; j += kPngThreads)
-      *reinterpret_cast<PngVec16 *>(raw + head + 16 * j) = *reinterpret_cast<const PngVec16 *>(g + head + 16 * j);
+      *reinterpret_cast<CodecVec16 *>(raw + head + 16 * j) = *reinterpret_cast<const CodecVec16 *>(g + head + 16 * j);
     const int done = head + 16 * nvec;
     if (tid < nraw - done) raw[done + tid] = g[done + tid];
   }
@@ -650,7 +629,7 @@ __global__ __launch_bounds__(kPngThreads) void png_segment(uint8_t *__restrict__
   uint8_t *slot = slots + ((long long)img * nseg + seg) * slot_bytes;
   const int nvec = (int)((nbytes + 15u) >> 4);
   for (int j = tid; j < nvec; j += kPngThreads)
-    reinterpret_cast<PngVec16 *>(slot)[j] = reinterpret_cast<const PngVec16 *>(obuf)[j];
+    reinterpret_cast<CodecVec16 *>(slot)[j] = reinterpret_cast<const CodecVec16 *>(obuf)[j];
   if (tid == 0) {
     uint32_t *m = meta + ((long long)img * nseg + seg) * kPngMetaWords;
     m[0] = nbytes;
@@ -659,14 +638,20 @@ __global__ __launch_bounds__(kPngThreads) void png_segment(uint8_t *__restrict__
   }
 }
 
+// dynamic LDS of png_assemble and png_finish in words: the kernels carve at these offsets, the launches pass the totals
+constexpr int kPngAsmRed = 256, kPngAsmSum = kPngAsmRed + kPngThreads, kPngAsmLdsWords = kPngAsmSum + 4;
+constexpr int kPngFinSum = kPngThreads, kPngFinStage = kPngFinSum + 4, kPngFinStageBytes = 64;
+constexpr int kPngFinLdsBytes = kPngFinStage * 4 + kPngFinStageBytes;
+static_assert(kPngHeadBytes <= kPngFinStageBytes && kPngTailBytes <= kPngFinStageBytes, "png_finish stages the head and the tail");
+
 // The segment's bytes to their place in the file, and their CRC.  Dynamic LDS: crc table [256], slice CRCs [256], sum [4].
 __global__ __launch_bounds__(kPngThreads) void png_assemble(uint8_t *__restrict__ out, long long out_stride,
                                                             const uint8_t *__restrict__ slots, uint32_t *__restrict__ meta,
                                                             int slot_bytes) {
   HF_DYN_LDS;
   uint32_t *tab = reinterpret_cast<uint32_t *>(hf_dyn_lds);
-  uint32_t *red = tab + 256;
-  uint32_t *sum = red + 256;
+  uint32_t *red = tab + kPngAsmRed;
+  uint32_t *sum = tab + kPngAsmSum;
   const int tid = (int)threadIdx.x;
   const int seg = (int)blockIdx.x, nseg = (int)gridDim.x, img = (int)blockIdx.y;
   uint32_t *mimg = meta + (long long)img * nseg * kPngMetaWords;
@@ -675,31 +660,12 @@ __global__ __launch_bounds__(kPngThreads) void png_assemble(uint8_t *__restrict_
     for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ kCrcPoly : c >> 1;
     tab[tid] = c;
   }
-  if (tid == 0) sum[0] = 0;
-  __syncthreads();
-  uint32_t part = 0;
-  for (int s = tid; s < seg; s += kPngThreads) part += mimg[s * kPngMetaWords];
-  if (part) atomicAdd(&sum[0], part);
+  codec_sum_before<kPngThreads>(sum, seg, tid, [&](int s) { return mimg[s * kPngMetaWords]; });
   __syncthreads();
   const uint32_t off = sum[0];
   const uint32_t n = mimg[seg * kPngMetaWords];
   const uint8_t *src = slots + ((long long)img * nseg + seg) * slot_bytes;
-  const uint32_t *srcw = reinterpret_cast<const uint32_t *>(src);
-  uint8_t *dst = out + (long long)img * out_stride + kPngHeadBytes + off;
-
-  uint32_t head = (uint32_t)((4u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 3u)) & 3u);
-  if (head > n) head = n;
-  const uint32_t nw = (n - head) >> 2;
-  if ((uint32_t)tid < head) dst[tid] = src[tid];
-  uint32_t *dstw = reinterpret_cast<uint32_t *>(dst + head);
-  const uint32_t sh = (head & 3u) * 8u;
-  for (uint32_t j = (uint32_t)tid; j < nw; j += kPngThreads) {
-    const uint32_t wi = (head + 4u * j) >> 2;
-    const uint32_t w0 = srcw[wi];
-    dstw[j] = sh ? (w0 >> sh) | (srcw[wi + 1] << (32u - sh)) : w0;
-  }
-  const uint32_t done = head + 4u * nw;
-  if ((uint32_t)tid < n - done) dst[done + tid] = src[done + tid];
+  codec_copy_slot<kPngThreads>(out + (long long)img * out_stride + kPngHeadBytes + off, src, n, tid);
 
   // CRC: slices of whole source words
   const uint32_t words = (n + 3u) >> 2;
@@ -726,8 +692,8 @@ __global__ __launch_bounds__(kPngThreads) void png_finish(uint8_t *__restrict__ 
                                                           int nseg, int h, int w, int channels, int R) {
   HF_DYN_LDS;
   uint32_t *red = reinterpret_cast<uint32_t *>(hf_dyn_lds);
-  uint32_t *sum = red + 256;
-  uint8_t *stage = reinterpret_cast<uint8_t *>(sum + 4);
+  uint32_t *sum = red + kPngFinSum;
+  uint8_t *stage = reinterpret_cast<uint8_t *>(red + kPngFinStage);
   const int tid = (int)threadIdx.x, img = (int)blockIdx.x;
   const uint32_t *mimg = meta + (long long)img * nseg * kPngMetaWords;
   if (tid < 4) sum[tid] = 0;
@@ -758,23 +724,19 @@ __global__ __launch_bounds__(kPngThreads) void png_finish(uint8_t *__restrict__ 
   // signature, IHDR, IDAT length and type, zlib header
   const uint32_t idat_len = total + 11u;
   int n = 0;
-  stage[n++] = 0x89; stage[n++] = 'P'; stage[n++] = 'N'; stage[n++] = 'G';
-  stage[n++] = 0x0D; stage[n++] = 0x0A; stage[n++] = 0x1A; stage[n++] = 0x0A;
-  stage[n++] = 0; stage[n++] = 0; stage[n++] = 0; stage[n++] = 13;
-  stage[n++] = 'I'; stage[n++] = 'H'; stage[n++] = 'D'; stage[n++] = 'R';
-  stage[n++] = (uint8_t)((uint32_t)w >> 24); stage[n++] = (uint8_t)((uint32_t)w >> 16);
-  stage[n++] = (uint8_t)((uint32_t)w >> 8); stage[n++] = (uint8_t)w;
-  stage[n++] = (uint8_t)((uint32_t)h >> 24); stage[n++] = (uint8_t)((uint32_t)h >> 16);
-  stage[n++] = (uint8_t)((uint32_t)h >> 8); stage[n++] = (uint8_t)h;
+  n = png_put_be32(stage, n, 0x89504E47u);  // the signature
+  n = png_put_be32(stage, n, 0x0D0A1A0Au);
+  n = png_put_be32(stage, n, 13u);
+  n = png_put_be32(stage, n, 0x49484452u);  // IHDR
+  n = png_put_be32(stage, n, (uint32_t)w);
+  n = png_put_be32(stage, n, (uint32_t)h);
   stage[n++] = 8; stage[n++] = channels == 3 ? 2 : 0; stage[n++] = 0; stage[n++] = 0; stage[n++] = 0;
   uint32_t c = 0xFFFFFFFFu;
   for (int i = 12; i < 29; ++i) c = png_crc_byte(c, stage[i]);
-  c ^= 0xFFFFFFFFu;
-  stage[n++] = (uint8_t)(c >> 24); stage[n++] = (uint8_t)(c >> 16); stage[n++] = (uint8_t)(c >> 8); stage[n++] = (uint8_t)c;
-  stage[n++] = (uint8_t)(idat_len >> 24); stage[n++] = (uint8_t)(idat_len >> 16);
-  stage[n++] = (uint8_t)(idat_len >> 8); stage[n++] = (uint8_t)idat_len;
-  stage[n++] = 'I'; stage[n++] = 'D'; stage[n++] = 'A'; stage[n++] = 'T';
-  stage[n++] = 0x78; stage[n++] = 0x01;  // n == kPngHeadBytes
+  n = png_put_be32(stage, n, c ^ 0xFFFFFFFFu);
+  n = png_put_be32(stage, n, idat_len);
+  n = png_put_be32(stage, n, 0x49444154u);  // IDAT
+  stage[n++] = 0x78; stage[n++] = 0x01;  // n == kPngHeadBytes: nine 32-bit values, five IHDR bytes, the zlib header
   for (int i = 0; i < kPngHeadBytes; ++i) o[i] = stage[i];
   uint32_t chead = 0xFFFFFFFFu;
   for (int i = 37; i < kPngHeadBytes; ++i) chead = png_crc_byte(chead, stage[i]);
@@ -782,16 +744,16 @@ __global__ __launch_bounds__(kPngThreads) void png_finish(uint8_t *__restrict__ 
   // final empty stored block, Adler-32
   n = 0;
   stage[n++] = 1; stage[n++] = 0; stage[n++] = 0; stage[n++] = 0xFF; stage[n++] = 0xFF;
-  stage[n++] = (uint8_t)(adler >> 24); stage[n++] = (uint8_t)(adler >> 16); stage[n++] = (uint8_t)(adler >> 8); stage[n++] = (uint8_t)adler;
+  n = png_put_be32(stage, n, adler);
   uint32_t ctail = 0xFFFFFFFFu;
   for (int i = 0; i < 9; ++i) ctail = png_crc_byte(ctail, stage[i]);
   ctail ^= 0xFFFFFFFFu;
   uint32_t crc = png_crc_mul(chead, png_crc_xpow8(total + 9u)) ^ ctail;
   for (int t = 0; t < kPngThreads; ++t) crc ^= red[t];
-  stage[n++] = (uint8_t)(crc >> 24); stage[n++] = (uint8_t)(crc >> 16); stage[n++] = (uint8_t)(crc >> 8); stage[n++] = (uint8_t)crc;
-  stage[n++] = 0; stage[n++] = 0; stage[n++] = 0; stage[n++] = 0;
-  stage[n++] = 'I'; stage[n++] = 'E'; stage[n++] = 'N'; stage[n++] = 'D';
-  stage[n++] = 0xAE; stage[n++] = 0x42; stage[n++] = 0x60; stage[n++] = 0x82;  // n == kPngTailBytes
+  n = png_put_be32(stage, n, crc);
+  n = png_put_be32(stage, n, 0u);
+  n = png_put_be32(stage, n, 0x49454E44u);  // IEND
+  n = png_put_be32(stage, n, 0xAE426082u);  // and its CRC; n == kPngTailBytes: the stored block's five bytes, five values
   uint8_t *tail = o + kPngHeadBytes + total;
   for (int i = 0; i < kPngTailBytes; ++i) tail[i] = stage[i];
   sizes[img] = (long long)kPngHeadBytes + total + kPngTailBytes;
@@ -857,10 +819,10 @@ extern "C" int hf_png_encode_u8(unsigned char *out, long long out_stride, long l
   hipLaunchKernelGGL(png_segment, dim3(s.nseg, batch), dim3(kPngThreads), lds, st, slots, meta, in, h, s.rb, channels, s.R, filter,
                      (int)s.slot, lds_filt, lds_obuf);
   if (hf_launch_status() != HF_OK) return HF_E_LAUNCH;
-  hipLaunchKernelGGL(png_assemble, dim3(s.nseg, batch), dim3(kPngThreads), (256 + 256 + 4) * 4, st, out, out_stride, slots, meta,
+  hipLaunchKernelGGL(png_assemble, dim3(s.nseg, batch), dim3(kPngThreads), kPngAsmLdsWords * 4, st, out, out_stride, slots, meta,
                      (int)s.slot);
   if (hf_launch_status() != HF_OK) return HF_E_LAUNCH;
-  hipLaunchKernelGGL(png_finish, dim3(batch), dim3(kPngThreads), (256 + 4) * 4 + 64, st, out, out_stride, sizes, meta, s.nseg, h, w,
+  hipLaunchKernelGGL(png_finish, dim3(batch), dim3(kPngThreads), kPngFinLdsBytes, st, out, out_stride, sizes, meta, s.nseg, h, w,
                      channels, s.R);
   return hf_launch_status();
 }

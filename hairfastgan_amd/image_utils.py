@@ -319,6 +319,11 @@ def _u8_images(images, what):
     raise ValueError(f"{what}: expected [B,H,W,3], [B,H,W,1], [B,H,W], [H,W,3] or [H,W]; got {tuple(images.shape)}")
 
 
+def _fetch_encoded(x, single, encoded):
+    files = fetch_files(*encoded)  # encoded: (files, sizes) of the batch x
+    return files[0] if single else [files[k] for k in range(x.shape[0])]
+
+
 def encode_png(images, filter="adaptive"):
     """uint8 images on the GPU - [B,H,W,3], [B,H,W,1], [B,H,W], [H,W,3] or [H,W] - -> list of B complete PNG files as
     `bytes` (a single image: `bytes`), RGB or greyscale, encoded on the device (hf_png_encode_u8: row filters, one
@@ -329,8 +334,7 @@ def encode_png(images, filter="adaptive"):
     if filter not in PNG_FILTERS:
         raise ValueError(f"filter must be one of {tuple(PNG_FILTERS)}; got {filter!r}")
     require_gpu(x)
-    files = fetch_files(*M.png_encode(lib(), stream(), x, PNG_FILTERS[filter]))
-    return files[0] if single else [files[k] for k in range(x.shape[0])]
+    return _fetch_encoded(x, single, M.png_encode(lib(), stream(), x, PNG_FILTERS[filter]))
 
 
 def encode_jpeg(images, quality=75, subsampling="4:2:0"):
@@ -345,8 +349,7 @@ def encode_jpeg(images, quality=75, subsampling="4:2:0"):
     x, single = _u8_images(images, "encode_jpeg")
     _check_jpeg(quality, subsampling)
     require_gpu(x)
-    files = fetch_files(*M.jpeg_encode(lib(), stream(), x, quality, JPEG_SUBSAMPLINGS[subsampling]))
-    return files[0] if single else [files[k] for k in range(x.shape[0])]
+    return _fetch_encoded(x, single, M.jpeg_encode(lib(), stream(), x, quality, JPEG_SUBSAMPLINGS[subsampling]))
 
 
 def save_images(images, paths, value_range=(0, 1), rounding="nearest", encoder="device", format=None, quality=75,

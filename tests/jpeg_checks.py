@@ -16,9 +16,8 @@ import torch
 
 from hairfastgan_amd import _marshal as M
 from tests import jpeg_ref as R
-from tests.png_checks import smooth
+from tests.png_checks import guarded_encode, smooth
 
-GUARD = 37          # bytes behind each slot (odd: the slots after the first start off every alignment)
 SHAPES = [(1, 1), (8, 8), (7, 13), (16, 16), (17, 9), (9, 33), (24, 40), (37, 53)]  # 24x40: the padding-order case
 MODES = ["grey", 0, 1, 2]
 QUALITIES = [10, 75, 95, 100]
@@ -69,31 +68,9 @@ def encode(L, st, device, images, quality=75, sub=2, base_offset=0):
     b, h, w, c = images.shape
     bound = int(L.hf_jpeg_bound(h, w, c, sub))
     assert 0 < bound <= bound_from_tables(h, w, c, sub), (bound, bound_from_tables(h, w, c, sub))  # no licence to waste
-    stride = bound + GUARD
-    src = torch.zeros(images.size + base_offset, dtype=torch.uint8, device=device)
-    src[base_offset:] = torch.from_numpy(images.reshape(-1)).to(device)
-    view = src[base_offset:]
-    assert view.data_ptr() % 16 == base_offset % 16
-    before = view.clone()
-    files = torch.full((b * stride + GUARD,), 0xA5, dtype=torch.uint8, device=device)
-    sizes = torch.full((b,), -1, dtype=torch.int64, device=device)
     ws_bytes = int(L.hf_jpeg_workspace_bytes(b, h, w, c, sub))
-    assert ws_bytes > 0
-    ws = torch.full((ws_bytes // 8 + 2 + GUARD,), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64, device=device)
-    M.check(L, L.hf_jpeg_encode_u8(files.data_ptr(), stride, sizes.data_ptr(), view.data_ptr(), b, h, w, c, quality, sub,
-                                   ws.data_ptr(), ws_bytes, st), "hf_jpeg_encode_u8")
-    files, sizes, ws = files.cpu().numpy(), sizes.cpu().numpy(), ws.cpu().numpy()
-    assert torch.equal(view, before), "the input was written"
-    assert (ws.view(np.uint8)[(ws_bytes + 7) // 8 * 8:] == 0x5A).all(), "written past the workspace"
-    assert (files[b * stride:] == 0xA5).all(), "written past the buffer"
-    out = []
-    for i in range(b):
-        assert 0 < sizes[i] <= bound, (i, sizes[i], bound)
-        slot = files[i * stride:(i + 1) * stride]
-        assert (slot[bound:] == 0xA5).all(), f"image {i}: written past hf_jpeg_bound"
-        assert (slot[sizes[i]:bound] == 0xA5).all(), f"image {i}: written past its own length"
-        out.append(slot[:sizes[i]].tobytes())
-    return out
+    return guarded_encode(L, device, images, "jpeg", bound, ws_bytes, lambda out, stride, sizes, src, ws: L.hf_jpeg_encode_u8(
+        out, stride, sizes, src, b, h, w, c, quality, sub, ws, ws_bytes, st), base_offset)
 
 
 def where_differs(got, ref):

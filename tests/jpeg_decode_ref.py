@@ -335,52 +335,11 @@ def flat_tables():
 def write(blocks, h, w, sampling=(1, 1), qtables=None, dc_tables=None, ac_tables=None, ri=0, sof=0xC0, comment=b""):
     """blocks: per component int [block rows, block columns, 64] in zig-zag order, whole MCUs (1 or 3 components; the first
     has `sampling`, the others 1x1).  qtables: per component 64 steps in natural order (default 1).  dc_tables / ac_tables:
-    (luma, chroma) as (bits, symbols) (default Annex K).  ri: MCUs per restart interval, 0 for none."""
+    (luma, chroma) as (bits, symbols) (default Annex K).  ri: MCUs per restart interval, 0 for none.  The file is assembled
+    by tests/jpeg_ref.py's `write_file`, the writer of the encoder's reference: component k uses quantisation table k."""
     nc = len(blocks)
-    samp = [sampling] + [(1, 1)] * (nc - 1)
-    qtables = qtables if qtables is not None else [np.ones(64, np.int64)] * nc
-    dc_tables = dc_tables or (E.DC_LUMA, E.DC_CHROMA)
-    ac_tables = ac_tables or (E.AC_LUMA, E.AC_CHROMA)
-    tabs = [0] + [1] * (nc - 1)
-    hmax, vmax = sampling
-    mcu_rows, mcu_cols = -(-h // (8 * vmax)), -(-w // (8 * hmax))
-    for b, (hs, vs) in zip(blocks, samp):
-        assert b.shape == (mcu_rows * vs, mcu_cols * hs, 64), (b.shape, mcu_rows, mcu_cols)
-    hist = collections.Counter()
-    dc = [E.huffman_codes(t) for t in dc_tables]
-    ac = [E.huffman_codes(t) for t in ac_tables]
-    total = mcu_rows * mcu_cols
-    per = ri if ri else total
-    out = bytearray(b"\xFF\xD8")
-    out += E.segment(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
-    if comment:
-        out += E.segment(0xFE, comment)
-    for t in range(nc):
-        out += E.segment(0xDB, bytes([t]) + bytes(int(v) for v in np.asarray(qtables[t])[ZIGZAG]))
-    body = bytes([8]) + h.to_bytes(2, "big") + w.to_bytes(2, "big") + bytes([nc])
-    for ci, (hs, vs) in enumerate(samp):
-        body += bytes([ci + 1, hs << 4 | vs, ci])
-    out += E.segment(sof, body)
-    for t in range(2 if nc == 3 else 1):
-        out += E.segment(0xC4, bytes([t]) + bytes(dc_tables[t][0]) + bytes(dc_tables[t][1]))
-        out += E.segment(0xC4, bytes([0x10 | t]) + bytes(ac_tables[t][0]) + bytes(ac_tables[t][1]))
-    if ri:
-        out += E.segment(0xDD, ri.to_bytes(2, "big"))
-    sos = bytes([nc])
-    for ci, t in enumerate(tabs):
-        sos += bytes([ci + 1, t << 4 | t])
-    out += E.segment(0xDA, sos + b"\x00\x3F\x00")
-    for i in range(-(-total // per)):
-        bw = E._Bits(hist)
-        pred = [0] * nc
-        for m in range(i * per, min(total, (i + 1) * per)):
-            my, mx = divmod(m, mcu_cols)
-            for ci, ((hs, vs), t) in enumerate(zip(samp, tabs)):
-                for by in range(vs):
-                    for bx in range(hs):
-                        pred[ci] = E.encode_block(bw, blocks[ci][my * vs + by, mx * hs + bx], pred[ci], dc[t], ac[t], hist)
-        bw.flush()
-        if i:
-            out += bytes([0xFF, 0xD0 + (i - 1) % 8])
-        out += bw.out
-    return bytes(out + b"\xFF\xD9")
+    data, _, _ = E.write_file(blocks, h, w, samp=[sampling] + [(1, 1)] * (nc - 1),
+                              qtables=qtables if qtables is not None else [np.ones(64, np.int64)] * nc, tq=list(range(nc)),
+                              tabs=[0] + [1] * (nc - 1), dc_tables=dc_tables or (E.DC_LUMA, E.DC_CHROMA),
+                              ac_tables=ac_tables or (E.AC_LUMA, E.AC_CHROMA), ri=ri, sof=sof, comment=comment)
+    return data

@@ -4,6 +4,7 @@ integer arithmetic (not from csrc/jpeg.h): the oracle of the device encoder's te
 byte for byte.
 
     encode(image uint8 [H,W,3] | [H,W,1] | [H,W], quality, subsampling) -> Encoded(data, blocks, hist, intervals)
+    write_file(blocks, h, w, ...)  -> the file of given coefficient blocks and tables (tests/jpeg_decode_ref.py's `write`)
 
 The pipeline, in libjpeg's order:
 1. RGB -> YCbCr in 16-bit fixed point (jccolor.c); grey input is its own single component;
@@ -275,14 +276,34 @@ def encode(image, quality=75, subsampling=2):
                         luma[y, x, 0] = prev
                     prev = luma[y, x, 0]
 
+    data, hist, intervals = write_file(blocks, h, w, samp=samp, qtables=qt[:len(set(tabs))], tq=tabs, tabs=tabs,
+                                       dc_tables=(DC_LUMA, DC_CHROMA), ac_tables=(AC_LUMA, AC_CHROMA), ri=mcu_cols)
+    return Encoded(data, blocks, hist, intervals)
+
+
+def write_file(blocks, h, w, samp, qtables, tq, tabs, dc_tables, ac_tables, ri=0, sof=0xC0, comment=b""):
+    """A baseline file from quantised blocks, the markers in libjpeg's order (jcmarker.c) with the JFIF APP0 Pillow sets.
+    blocks: per component int [block rows, block columns, 64] in zig-zag order, whole MCUs; samp: per component (hs, vs), the
+    first the largest; qtables: the quantisation tables to define, 64 steps in natural order each, table t as number t; tq /
+    tabs: per component the number of its quantisation table / of its Huffman tables; dc_tables / ac_tables: (luma, chroma)
+    as (bits, symbols); ri: MCUs per restart interval, 0 for none (and no DRI); sof: the frame marker; comment: a COM
+    segment.  -> (the file, Counter of coded symbols, the entropy-coded bytes of every restart interval)."""
+    nc = len(blocks)
+    hmax, vmax = samp[0]
+    mcu_rows, mcu_cols = -(-h // (8 * vmax)), -(-w // (8 * hmax))
+    for b, (hs, vs) in zip(blocks, samp):
+        assert b.shape == (mcu_rows * vs, mcu_cols * hs, 64), (b.shape, mcu_rows, mcu_cols)
     hist = collections.Counter()
-    dc = [huffman_codes(DC_LUMA), huffman_codes(DC_CHROMA)]
-    ac = [huffman_codes(AC_LUMA), huffman_codes(AC_CHROMA)]
+    dc = [huffman_codes(t) for t in dc_tables]
+    ac = [huffman_codes(t) for t in ac_tables]
+    total = mcu_rows * mcu_cols
+    per = ri if ri else total
     intervals = []
-    for my in range(mcu_rows):
+    for i in range(-(-total // per)):
         bw = _Bits(hist)
-        pred = [0] * len(planes)
-        for mx in range(mcu_cols):
+        pred = [0] * nc
+        for m in range(i * per, min(total, (i + 1) * per)):
+            my, mx = divmod(m, mcu_cols)
             for ci, ((hs, vs), t) in enumerate(zip(samp, tabs)):
                 for by in range(vs):
                     for bx in range(hs):
@@ -292,17 +313,20 @@ def encode(image, quality=75, subsampling=2):
 
     out = bytearray(b"\xFF\xD8")
     out += segment(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
-    for t in range(2 if c == 3 else 1):
-        out += segment(0xDB, bytes([t]) + bytes(int(v) for v in qt[t][ZIGZAG]))
-    sof = bytes([8]) + h.to_bytes(2, "big") + w.to_bytes(2, "big") + bytes([len(planes)])
-    for ci, ((hs, vs), t) in enumerate(zip(samp, tabs)):
-        sof += bytes([ci + 1, hs << 4 | vs, t])
-    out += segment(0xC0, sof)
-    for t in range(2 if c == 3 else 1):
-        for cls, table in ((0, (DC_LUMA, DC_CHROMA)[t]), (1, (AC_LUMA, AC_CHROMA)[t])):
+    if comment:
+        out += segment(0xFE, comment)
+    for t, table in enumerate(qtables):
+        out += segment(0xDB, bytes([t]) + bytes(int(v) for v in np.asarray(table)[ZIGZAG]))
+    frame = bytes([8]) + h.to_bytes(2, "big") + w.to_bytes(2, "big") + bytes([nc])
+    for ci, ((hs, vs), t) in enumerate(zip(samp, tq)):
+        frame += bytes([ci + 1, hs << 4 | vs, t])
+    out += segment(sof, frame)
+    for t in range(2 if nc == 3 else 1):
+        for cls, table in ((0, dc_tables[t]), (1, ac_tables[t])):
             out += segment(0xC4, bytes([cls << 4 | t]) + bytes(table[0]) + bytes(table[1]))
-    out += segment(0xDD, mcu_cols.to_bytes(2, "big"))
-    sos = bytes([len(planes)])
+    if ri:
+        out += segment(0xDD, ri.to_bytes(2, "big"))
+    sos = bytes([nc])
     for ci, t in enumerate(tabs):
         sos += bytes([ci + 1, t << 4 | t])
     out += segment(0xDA, sos + b"\x00\x3F\x00")
@@ -311,7 +335,7 @@ def encode(image, quality=75, subsampling=2):
             out += bytes([0xFF, 0xD0 + (k - 1) % 8])
         out += data
     out += b"\xFF\xD9"
-    return Encoded(bytes(out), blocks, hist, intervals)
+    return bytes(out), hist, intervals
 
 
 def pil_encode(image, quality=75, subsampling=2):

@@ -92,14 +92,12 @@ def segment_rows(L, h, w, c):
     return int(L.hf_png_segment_rows(h, w, c))
 
 
-def encode(L, st, device, images, filter_mode=3, base_offset=0):
-    """images: numpy uint8 [B,H,W,C] -> list of file bytes; every structural assertion that needs no decoding."""
-    images = np.ascontiguousarray(images)
-    b, h, w, c = images.shape
-    bound = int(L.hf_png_bound(h, w, c))
-    r = segment_rows(L, h, w, c)
-    n = h * (w * c + 1)
-    assert 0 < bound <= n + 5 * -(-n // 65535) + 5 * -(-h // r) + 128, (bound, n, r)  # the bound is no licence to waste
+def guarded_encode(L, device, images, codec, bound, ws_bytes, call, base_offset=0):
+    """The guarded-buffer protocol of the codecs' `encode`: images (numpy uint8 [B,H,W,C], contiguous) at `base_offset` inside
+    16 bytes, 0xA5 behind every slot of `bound` bytes and behind the buffer, 0x5A behind the workspace of `ws_bytes`;
+    call(files, stride, sizes, source, workspace) -> the status of hf_<codec>_encode_u8.  The input is unchanged, the sizes
+    lie within the bound, nothing is written past a file's own length; -> list of file bytes."""
+    b = images.shape[0]
     stride = bound + GUARD
     src = torch.zeros(images.size + base_offset, dtype=torch.uint8, device=device)
     src[base_offset:] = torch.from_numpy(images.reshape(-1)).to(device)
@@ -108,11 +106,9 @@ def encode(L, st, device, images, filter_mode=3, base_offset=0):
     before = view.clone()
     files = torch.full((b * stride + GUARD,), 0xA5, dtype=torch.uint8, device=device)
     sizes = torch.full((b,), -1, dtype=torch.int64, device=device)
-    ws_bytes = int(L.hf_png_workspace_bytes(b, h, w, c))
     assert ws_bytes > 0
     ws = torch.full((ws_bytes // 8 + 2 + GUARD,), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64, device=device)
-    M.check(L, L.hf_png_encode_u8(files.data_ptr(), stride, sizes.data_ptr(), view.data_ptr(), b, h, w, c, filter_mode,
-                                  ws.data_ptr(), ws_bytes, st), "hf_png_encode_u8")
+    M.check(L, call(files.data_ptr(), stride, sizes.data_ptr(), view.data_ptr(), ws.data_ptr()), f"hf_{codec}_encode_u8")
     files, sizes, ws = files.cpu().numpy(), sizes.cpu().numpy(), ws.cpu().numpy()
     assert torch.equal(view, before), "the input was written"
     assert (ws.view(np.uint8)[(ws_bytes + 7) // 8 * 8:] == 0x5A).all(), "written past the workspace"
@@ -121,10 +117,23 @@ def encode(L, st, device, images, filter_mode=3, base_offset=0):
     for i in range(b):
         assert 0 < sizes[i] <= bound, (i, sizes[i], bound)
         slot = files[i * stride:(i + 1) * stride]
-        assert (slot[bound:] == 0xA5).all(), f"image {i}: written past hf_png_bound"
+        assert (slot[bound:] == 0xA5).all(), f"image {i}: written past hf_{codec}_bound"
         assert (slot[sizes[i]:bound] == 0xA5).all(), f"image {i}: written past its own length"
         out.append(slot[:sizes[i]].tobytes())
     return out
+
+
+def encode(L, st, device, images, filter_mode=3, base_offset=0):
+    """images: numpy uint8 [B,H,W,C] -> list of file bytes; every structural assertion that needs no decoding."""
+    images = np.ascontiguousarray(images)
+    b, h, w, c = images.shape
+    bound = int(L.hf_png_bound(h, w, c))
+    r = segment_rows(L, h, w, c)
+    n = h * (w * c + 1)
+    assert 0 < bound <= n + 5 * -(-n // 65535) + 5 * -(-h // r) + 128, (bound, n, r)  # the bound is no licence to waste
+    ws_bytes = int(L.hf_png_workspace_bytes(b, h, w, c))
+    return guarded_encode(L, device, images, "png", bound, ws_bytes, lambda out, stride, sizes, src, ws: L.hf_png_encode_u8(
+        out, stride, sizes, src, b, h, w, c, filter_mode, ws, ws_bytes, st), base_offset)
 
 
 def check_roundtrip(L, st, device, images, filter_mode=3, base_offset=0):
