@@ -82,6 +82,7 @@ SIGNATURES = {
     "hf_png_encode_u8": [_f, _ll, _f, _f, _i, _i, _i, _i, _i, _f, _ll, _st],
     "hf_jpeg_encode_u8": [_f, _ll, _f, _f, _i, _i, _i, _i, _i, _i, _f, _ll, _st],
     "hf_jpeg_decode_u8": [_f, _f, _f, _f, _ll, _f, _ll, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _ll, _st],
+    "hf_png_decode_u8": [_f, _f, _f, _f, _ll, _f, _ll, _f, _i, _i, _i, _i, _i, _i, _f, _ll, _st],
     "hf_maxpool3x3s2_f32":[_f, _f, _ll, _i, _i, _st],
     "hf_gate_f32": [_f, _f, _f, _f, _f, _fl, _ll, _i, _st],
     "hf_upsample_nearest_f32": [_f, _f, _ll, _i, _i, _i, _i, _st],
@@ -129,6 +130,7 @@ SIGNATURES = {
     "hf_jpeg_chunk_mcus": [_i, _i],
     "hf_jpeg_workspace_bytes": (_ll, [_i, _i, _i, _i, _i]),
     "hf_jpeg_decode_workspace_bytes": (_ll, [_i, _i, _i, _i, _i, _i, _i, _ll]),
+    "hf_png_decode_workspace_bytes": (_ll, [_i, _i, _i, _i, _ll]),
 }
 
 

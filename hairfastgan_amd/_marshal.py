@@ -1567,3 +1567,42 @@ def jpeg_decode(lib, st, scans, offsets, max_scan_bytes, tables, h, w, component
                                      int(max_scan_bytes), _p(tables), b, h, w, components, hs, vs, restart_interval, out_channels,
                                      int(sub_bytes), _p(ws), ws.numel() * 8, st), "hf_jpeg_decode_u8")
     return out, outf, status
+
+
+PNG_COLOR_CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}  # colour type -> samples per pixel in the file
+PNG_DECODE_ERRORS = {1: "truncated stream", 2: "block type 3", 3: "a stored block whose LEN is not the complement of NLEN",
+                     4: "an invalid set of code lengths (over-subscribed, incomplete, a repeat past the end, or no end-of-block code)",
+                     5: "repeat code 16 with no previous length", 6: "more than 286 literal/length or 30 distance codes",
+                     7: "a code that is not in the Huffman table", 8: "length symbol 286 or 287", 9: "distance symbol 30 or 31",
+                     10: "a match distance beyond the bytes produced", 11: "more bytes than the image holds",
+                     12: "fewer bytes than the image holds", 13: "a filter type above 4", 14: "the Adler-32 does not match",
+                     15: "a bad zlib header"}
+
+
+def png_decode(lib, st, streams, offsets, max_stream_bytes, palettes, h, w, color_type, out_channels=3, u8=True, f32=False,
+               token_cap=0):
+    """The zlib streams of B PNG files of one geometry (csrc/png_decode.h) -> (uint8 [B,H,W,out_channels] or None, float32
+    [B,out_channels,H,W] or None, status int32 [B,2]) on the streams' device.  streams: uint8 [N]; offsets: int64 [B+1];
+    palettes: uint8 [B,256,3] for colour type 3, else None.  Nothing is synchronised: the caller reads status."""
+    if streams.dtype != torch.uint8 or offsets.dtype != torch.int64 or (palettes is not None and palettes.dtype != torch.uint8):
+        raise TypeError(f"expected uint8 streams and palettes, int64 offsets; got {streams.dtype}, {offsets.dtype}")
+    if offsets.ndim != 1 or offsets.numel() < 2:
+        raise ValueError(f"expected offsets [B+1]; got {tuple(offsets.shape)}")
+    b, dev = offsets.numel() - 1, streams.device
+    if color_type == 3 and (palettes is None or tuple(palettes.shape) != (b, 256, 3)):
+        raise ValueError(f"colour type 3 needs palettes [B,256,3]; got {None if palettes is None else tuple(palettes.shape)}")
+    if not (u8 or f32):
+        raise ValueError("one of u8 and f32 must be asked for")
+    if not (streams.is_contiguous() and offsets.is_contiguous() and (palettes is None or palettes.is_contiguous())) or streams.numel() == 0:
+        raise ValueError("streams, offsets and palettes must be contiguous and not empty")
+    ws_bytes = lib.hf_png_decode_workspace_bytes(b, h, w, color_type, int(max_stream_bytes))
+    if ws_bytes <= 0:
+        raise ValueError(f"hf_png_decode_u8 does not take {b} files of {h}x{w}, colour type {color_type}")
+    out = torch.empty((b, h, w, out_channels), dtype=torch.uint8, device=dev) if u8 else None
+    outf = torch.empty((b, out_channels, h, w), dtype=torch.float32, device=dev) if f32 else None
+    status = torch.empty((b, 2), dtype=torch.int32, device=dev)
+    ws = torch.empty((ws_bytes + 15) // 16 * 2, dtype=torch.int64, device=dev)
+    check(lib, lib.hf_png_decode_u8(_p(out) if u8 else None, _p(outf) if f32 else None, _p(status), _p(streams), streams.numel(), _p(offsets),
+                                    int(max_stream_bytes), _p(palettes) if color_type == 3 else None, b, h, w, color_type, out_channels,
+                                    int(token_cap), _p(ws), ws.numel() * 8, st), "hf_png_decode_u8")
+    return out, outf, status

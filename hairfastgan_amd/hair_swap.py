@@ -66,7 +66,8 @@ def get_parser():
     parser.add_argument("--png_encoder", choices=("pil", "device"), default="pil",
                         help="who makes the PNG files of --save_all: PIL (zlib on the host) or the GPU (image_utils.encode_png)")
     parser.add_argument("--image_decoder", choices=("pil", "device"), default="pil",
-                        help="who decodes JPEG files given as paths: PIL (libjpeg on the host) or the GPU (image_utils.decode_jpeg)")
+                        help="who decodes JPEG and PNG files given as paths: PIL (libjpeg / zlib on the host) or the GPU "
+                             "(image_utils.decode_jpeg / decode_png; a PNG file the device does not take, 16-bit or interlaced, stays with PIL)")
     parser.add_argument("--mixing", type=float, default=0.95)
     parser.add_argument("--smooth", type=int, default=5)
     parser.add_argument("--rotate_checkpoint", type=str, default="pretrained_models/Rotate/rotate_best.pth")
@@ -983,23 +984,36 @@ class HairFast:
 
     def _decode_paths(self, images, cache):
         """args.image_decoder == "device": every distinct path among `images` whose file begins with FF D8 is decoded by
-        `image_utils.decode_jpeg` in ONE call and enters `cache` as uint8 [3,H,W] on the device, where `_as_tensor` finds it;
-        a JPEG file the device decoder does not take raises (no fallback to PIL).  -> the ids of those tensors."""
+        `image_utils.decode_jpeg` in ONE call, every one that is a PNG file whose header `parse_png_header` accepts by
+        `image_utils.decode_png` in ONE call; they enter `cache` as uint8 [3,H,W] on the device, where `_as_tensor` finds
+        them.  A JPEG file the device decoder does not take raises, and so does a corrupt stream of either kind (no fallback
+        to PIL); a PNG file whose header is refused (16-bit, interlaced, 1/2/4-bit) keeps the route through PIL.
+        -> the ids of the decoded tensors."""
         if getattr(self.args, "image_decoder", "pil") != "device":
             return set()
-        from .image_utils import decode_jpeg
+        from .image_utils import PNG_SIGNATURE, decode_jpeg, decode_png, parse_png_header
 
-        paths = []
+        jpegs, pngs = [], {}
         for img in images:
-            if isinstance(img, (Path, str)) and img not in cache and img not in paths and not str(img).endswith(".npy"):
+            if isinstance(img, (Path, str)) and img not in cache and img not in jpegs and img not in pngs and not str(img).endswith(".npy"):
                 with open(img, "rb") as fh:
-                    if fh.read(2) == b"\xFF\xD8":
-                        paths.append(img)
-        if not paths:
-            return set()
-        for img, t in zip(paths, decode_jpeg([str(p) for p in paths], device=self.args.device)):
-            cache[img] = t.permute(2, 0, 1).contiguous()
-        return {id(cache[img]) for img in paths}
+                    head = fh.read(8)
+                    if head[:2] == b"\xFF\xD8":
+                        jpegs.append(img)
+                    elif head == PNG_SIGNATURE:
+                        data = head + fh.read()
+                        try:
+                            parse_png_header(data)
+                        except ValueError:
+                            continue
+                        pngs[img] = data
+        if jpegs:
+            for img, t in zip(jpegs, decode_jpeg([str(p) for p in jpegs], device=self.args.device)):
+                cache[img] = t.permute(2, 0, 1).contiguous()
+        if pngs:
+            for img, t in zip(pngs, decode_png(list(pngs.values()), device=self.args.device)):
+                cache[img] = t.permute(2, 0, 1).contiguous()
+        return {id(cache[img]) for img in list(jpegs) + list(pngs)}
 
     def _beside_decoded(self, images, decoded):
         """With files decoded on the device among `images`, the CPU tensors beside them (other files, PIL images, arrays)

@@ -35,6 +35,9 @@ the host.  `encode_png` / `save_images` / `save_image(encoder="device")` make th
 same for JPEG (hf_jpeg_encode_u8): the file Pillow's libjpeg would write, without the pixels crossing to the host.
 `decode_jpeg` / `read_images(decoder="device")` are the way back (hf_jpeg_decode_u8): the host reads a baseline JPEG file's
 header segments, the entropy-coded bytes go to the device as they are and the pixels Pillow would return are made there.
+`decode_png` does the same for PNG files (hf_png_decode_u8): the host walks the chunks, the IDAT payloads go to the device as
+they are, and inflate, the Adler-32, the row filters and the pixel conversion run there; `read_images(decoder="device")`
+sends each file to the decoder of its kind.
 """
 from types import SimpleNamespace
 
@@ -558,14 +561,162 @@ def decode_jpeg(files, mode="RGB", dtype=torch.uint8, device="cuda", sub_bytes=0
     return results[0] if single else results
 
 
+# ---------------------------------------------------------------------------------------------
+# PNG files decoded on the device (csrc/png_decode.h)
+# ---------------------------------------------------------------------------------------------
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+PNG_MODES = ("RGB", "unchanged")
+
+
+def parse_png_header(data):
+    """The chunks of a PNG file (pure Python, no GPU; no byte of the IDAT payloads is looked at) -> SimpleNamespace: height,
+    width, color_type, channels (samples per pixel in the file), palette (uint8 [256,3], a short PLTE padded with zeros),
+    idat (the (offset, length) pairs of the IDAT payloads in file order) and idat_bytes (their sum).  The CRC-32 of IHDR and
+    PLTE is checked; tRNS, gAMA, iCCP and every other ancillary chunk are ignored.  ValueError("unsupported PNG: ...") for
+    what the device decoder does not take: a bit depth other than 8, Adam7 interlace, an unknown colour type, compression
+    or filter method, a zero dimension, no IHDR, no IDAT, colour type 3 without PLTE."""
+    import zlib
+
+    data = bytes(data) if not isinstance(data, bytes) else data
+    if data[:8] != PNG_SIGNATURE:
+        raise ValueError("unsupported PNG: not a PNG file (no signature)")
+    pos, ihdr, palette, idat = 8, None, None, []
+    while pos + 8 <= len(data):
+        n, ctype = int.from_bytes(data[pos:pos + 4], "big"), data[pos + 4:pos + 8]
+        if pos + 12 + n > len(data):
+            if ctype == b"IDAT" or not idat:
+                raise ValueError("unsupported PNG: a truncated chunk")
+            break
+        if ctype in (b"IHDR", b"PLTE") and zlib.crc32(data[pos + 4:pos + 8 + n]) != int.from_bytes(data[pos + 8 + n:pos + 12 + n], "big"):
+            raise ValueError(f"unsupported PNG: the CRC of {ctype.decode()} does not match")
+        if pos == 8 and (ctype != b"IHDR" or n != 13):
+            raise ValueError("unsupported PNG: no IHDR chunk at the start")
+        if ctype == b"IHDR":
+            ihdr = data[pos + 8:pos + 21]
+        elif ctype == b"PLTE":
+            if n % 3 or n > 768:
+                raise ValueError("unsupported PNG: a bad PLTE chunk")
+            palette = np.zeros((256, 3), np.uint8)
+            palette[:n // 3] = np.frombuffer(data[pos + 8:pos + 8 + n], np.uint8).reshape(-1, 3)
+        elif ctype == b"IDAT":
+            idat.append((pos + 8, n))
+        elif ctype == b"IEND":
+            break
+        pos += 12 + n
+    if ihdr is None:
+        raise ValueError("unsupported PNG: no IHDR chunk at the start")
+    w, h = int.from_bytes(ihdr[0:4], "big"), int.from_bytes(ihdr[4:8], "big")
+    depth, color_type, compression, filter_method, interlace = ihdr[8:13]
+    if w == 0 or h == 0:
+        raise ValueError("unsupported PNG: a zero dimension")
+    if color_type not in M.PNG_COLOR_CHANNELS:
+        raise ValueError(f"unsupported PNG: colour type {color_type}")
+    if depth != 8:
+        raise ValueError(f"unsupported PNG: bit depth {depth}; 8 only")
+    if compression != 0 or filter_method != 0:
+        raise ValueError(f"unsupported PNG: compression method {compression}, filter method {filter_method}")
+    if interlace != 0:
+        raise ValueError("unsupported PNG: Adam7 interlace")
+    if not idat:
+        raise ValueError("unsupported PNG: no IDAT chunk")
+    if color_type == 3 and palette is None:
+        raise ValueError("unsupported PNG: colour type 3 without a PLTE chunk")
+    if palette is None:
+        palette = np.zeros((256, 3), np.uint8)
+    return SimpleNamespace(height=h, width=w, color_type=color_type, channels=M.PNG_COLOR_CHANNELS[color_type], palette=palette,
+                           idat=idat, idat_bytes=sum(n for _, n in idat))
+
+
+def _file_bytes(f, what):
+    if isinstance(f, (bytes, bytearray, memoryview)):
+        return bytes(f)
+    if isinstance(f, str) or hasattr(f, "__fspath__"):
+        with open(f, "rb") as fh:
+            return fh.read()
+    raise TypeError(f"{what}: expected bytes or a path; got {type(f)}")
+
+
+def decode_png(files, mode="RGB", dtype=torch.uint8, device="cuda", token_cap=0):
+    """PNG files - `bytes`, a path, or a list of either - decoded on the device (hf_png_decode_u8) ->
+    a device tensor (a list of them for a list): uint8 [H,W,3], the pixels of `PIL.Image.open(f).convert("RGB")` byte for
+    byte ("unchanged": the file's samples [H,W,1|2|3|4], a palette file expanded to 3); with dtype=torch.float32 [C,H,W] =
+    byte / 255 in the CPU's bits.  Bit depth 8, no interlace, colour types 0, 2, 3, 4 and 6.  The host walks the chunks and
+    concatenates the IDAT payloads; it inflates nothing.  Files of one geometry (height, width, colour type) share one set
+    of launches, all files one copy to the device and one synchronisation.  ValueError for a file the decoder does not take
+    (`parse_png_header`) or whose stream is corrupt; there is no fallback to PIL."""
+    if mode not in PNG_MODES:
+        raise ValueError(f"mode must be one of {PNG_MODES}; got {mode!r}")
+    if dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"dtype must be torch.uint8 or torch.float32; got {dtype}")
+    single = not isinstance(files, (list, tuple))
+    datas = [_file_bytes(f, "decode_png") for f in ([files] if single else files)]
+    if not datas:
+        return []
+    device = torch.device(device)
+    if device.type != "cuda":
+        require_gpu(torch.empty(0, device=device))
+    heads = [parse_png_header(d) for d in datas]
+    groups = {}
+    for k, hd in enumerate(heads):
+        groups.setdefault((hd.height, hd.width, hd.color_type), []).append(k)
+    # one host buffer: per group the offsets and (colour type 3) the palettes, then every stream; one copy
+    order = [k for ks in groups.values() for k in ks]
+    head_bytes = sum(8 * (len(ks) + 1) + 8 + (768 * len(ks) if key[2] == 3 else 0) for key, ks in groups.items())
+    head_bytes = (head_bytes + 15) // 16 * 16
+    host = np.zeros(head_bytes + sum(heads[k].idat_bytes for k in order) + 16, np.uint8)
+    pos, spos, layout = 0, head_bytes, []
+    for key, ks in groups.items():
+        off = host[pos:pos + 8 * (len(ks) + 1)].view(np.int64)
+        pal_at = pos + 8 * (len(ks) + 1)
+        start = spos
+        for j, k in enumerate(ks):
+            off[j] = spos - start
+            view = memoryview(datas[k])
+            for at, n in heads[k].idat:
+                host[spos:spos + n] = np.frombuffer(view[at:at + n], np.uint8)
+                spos += n
+            if key[2] == 3:
+                host[pal_at + 768 * j:pal_at + 768 * (j + 1)] = heads[k].palette.reshape(-1)
+        off[len(ks)] = spos - start
+        layout.append((key, ks, pos, pal_at, start, spos, max(heads[k].idat_bytes for k in ks)))
+        pos = pal_at + (768 * len(ks) if key[2] == 3 else 0)
+        pos = (pos + 7) // 8 * 8
+    blob = torch.from_numpy(host).to(device)
+    L, st = lib(), stream()
+    results, statuses = [None] * len(datas), []
+    for (h, w, ct), ks, off_at, pal_at, start, end, longest in layout:
+        oc = 3 if (mode == "RGB" or ct == 3) else M.PNG_COLOR_CHANNELS[ct]
+        u8, f32, status = M.png_decode(L, st, blob[start:max(end, start + 1)], blob[off_at:off_at + 8 * (len(ks) + 1)].view(torch.int64), longest,
+                                       blob[pal_at:pal_at + 768 * len(ks)].view(len(ks), 256, 3) if ct == 3 else None, h, w, ct, oc,
+                                       dtype is torch.uint8, dtype is torch.float32, token_cap)
+        statuses.append(status[:, 0])
+        for j, k in enumerate(ks):
+            results[k] = u8[j] if dtype is torch.uint8 else f32[j]
+    codes = torch.cat(statuses).cpu().tolist()  # the one synchronisation
+    for k, code in zip(order, codes):
+        if code:
+            raise ValueError(f"corrupt PNG (file {k}): {M.PNG_DECODE_ERRORS.get(code, code)}")
+    return results[0] if single else results
+
+
 def read_images(paths, decoder="pil"):
     """Image files -> list of uint8 [3,H,W] tensors, what `torchvision.io.read_image(path, mode=RGB)` gives: decoder="pil" on
-    the host (CPU tensors), "device" - JPEG files only - with `decode_jpeg` in one call (device tensors, views of [H,W,3])."""
+    the host (CPU tensors); "device" - PNG files (by their signature) with `decode_png`, JPEG files (FF D8) with `decode_jpeg`,
+    one call per kind, anything else a ValueError - device tensors, views of [H,W,3], in the order of `paths`."""
     if decoder not in DECODERS:
         raise ValueError(f"decoder must be one of {DECODERS}; got {decoder!r}")
     paths = list(paths)
     if decoder == "device":
-        return [t.permute(2, 0, 1) for t in decode_jpeg(paths)]
+        datas = [_file_bytes(p, "read_images") for p in paths]
+        kinds = ["png" if d[:8] == PNG_SIGNATURE else "jpeg" if d[:2] == b"\xFF\xD8" else None for d in datas]
+        if None in kinds:
+            raise ValueError(f"read_images(decoder='device'): neither a PNG nor a JPEG file: {paths[kinds.index(None)]}")
+        out = [None] * len(paths)
+        for kind, decode in (("png", decode_png), ("jpeg", decode_jpeg)):
+            ks = [k for k, x in enumerate(kinds) if x == kind]
+            for k, t in zip(ks, decode([datas[k] for k in ks]) if ks else []):
+                out[k] = t.permute(2, 0, 1)
+        return out
     from .hair_swap import _read_image_rgb
 
     return [_read_image_rgb(p) for p in paths]

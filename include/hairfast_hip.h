@@ -688,6 +688,34 @@ int hf_jpeg_decode_u8(unsigned char *out, float *out_f32, int *status, const uns
                       int components, int hs, int vs, int restart_interval, int out_channels, int sub_bytes, void *workspace,
                       long long workspace_bytes, void *stream);
 
+/* ---- a PNG decoder on the device (csrc/png_decode.h) ----
+ * hf_png_decode_u8: the zlib streams of `batch` PNG files of ONE geometry (h, w, color_type; bit depth 8, no interlace)
+ * -> uint8 images out [batch,h,w,out_channels] and / or float images out_f32 [batch,out_channels,h,w] = byte / 255 (IEEE
+ * division); either may be null, not both.  The pixels are those Pillow returns, byte for byte.  The caller walks each
+ * file's chunks and passes, in device memory:
+ *   streams [streams_bytes]   each file's IDAT payloads concatenated (one zlib stream); file b's are
+ *                             [stream_offsets[b], stream_offsets[b + 1]) (int64 [batch + 1], device; clamped to the
+ *                             buffer); max_stream_bytes: the longest of them (it sizes the candidate search)
+ *   palettes [batch][256][3]  for color_type 3 only (a short PLTE padded with zeros); else null
+ * color_type: 0 grey, 2 RGB, 3 palette, 4 grey + alpha, 6 RGBA.  out_channels: 3 (grey replicated, alpha dropped, the
+ * palette looked up), or the file's own samples: 1, 3, 3 (the palette looked up), 2, 4.  token_cap: tokens per round of the
+ * inflate kernel's token buffer, 2..2048, 0 for the default (1024).
+ * status: int32 [batch][2] (device): [b][0] is 0 or why file b could not be decoded, the largest of - 1 truncated stream,
+ * 2 block type 3, 3 stored LEN != ~NLEN, 4 an invalid set of code lengths, 5 repeat code 16 with no previous length,
+ * 6 more than 286 / 30 codes, 7 a code not in the table, 8 length symbol 286 / 287, 9 distance symbol 30 / 31, 10 a distance
+ * beyond the bytes produced, 11 too many bytes, 12 too few bytes, 13 a filter type above 4, 14 an Adler-32 mismatch, 15 a
+ * bad zlib header; the image is then undefined.  [b][1]: the segments of the stream that were decoded independently (those
+ * that produced bytes); 1 for a stream that took the serial route.  IDAT chunk CRCs are the caller's and are not checked.
+ * HF_E_INVALID: a null pointer, another colour type or channel count, a zero dimension, h * (w * channels + 1) or
+ * max_stream_bytes of 2 GiB or more, batch outside 1..65535, token_cap outside 2..2048, a misaligned workspace (16) /
+ * stream_offsets (8) / status, out_f32 (4).  HF_E_WORKSPACE: workspace_bytes < hf_png_decode_workspace_bytes (0 for a
+ * geometry that is not taken).  Nothing is launched then. */
+long long hf_png_decode_workspace_bytes(int batch, int h, int w, int color_type, long long max_stream_bytes);
+int hf_png_decode_u8(unsigned char *out, float *out_f32, int *status, const unsigned char *streams, long long streams_bytes,
+                     const long long *stream_offsets, long long max_stream_bytes, const unsigned char *palettes, int batch, int h,
+                     int w, int color_type, int out_channels, int token_cap, void *workspace, long long workspace_bytes,
+                     void *stream);
+
 /* ---- PostProcessModel's latent branch (models/Encoders.py:13-32, 119-131) ----
  * F.layer_norm over the last `dim` elements of each of `rows` rows (biased variance, eps inside the sqrt):
  * gamma / beta [dim] = elementwise affine (both NULL: LayerNorm(elementwise_affine=False), :19), lrelu != 0
