@@ -54,17 +54,21 @@ def _offset_view(t, dev, floats=1):
     return v
 
 
-def accuracy(op, label, got, ref64, t32, factor=FACTOR):
+def accuracy(op, label, got, ref64, t32, factor=FACTOR, extra=0.0, tag="small_ops"):
+    """extra: an additive term of the bound, a number or a tensor of ref64's shape (a per-element bound); the row then holds
+    E_k and the bound of the element whose E_k / bound is largest."""
     _sync(got.device)
     got = got.detach().cpu()
     assert got.shape == ref64.shape, (op, label, tuple(got.shape), tuple(ref64.shape))
     assert bool(torch.isfinite(got).all()), (op, label)
-    e_k = float((got.double() - ref64).abs().max())
+    err = (got.double() - ref64).abs()
     e_t = float((t32.double() - ref64).abs().max())
-    bound = factor * e_t + 4 * ULP * float(ref64.abs().max())
+    bounds = factor * e_t + 4 * ULP * float(ref64.abs().max()) + torch.as_tensor(extra, dtype=torch.float64).expand(err.shape)
+    i = int(torch.argmax(err / bounds.clamp_min(1e-300)))
+    e_k, bound = float(err.reshape(-1)[i]), float(bounds.reshape(-1)[i])
     ROWS.append((op, label, e_k, e_t, bound))
-    print(f"small_ops {op} {label}: E_k {e_k:.2e} E_t {e_t:.2e} bound {bound:.2e}")
-    assert e_k <= bound, (op, label, e_k, e_t, bound)
+    print(f"{tag} {op} {label}: E_k {e_k:.2e} E_t {e_t:.2e} bound {bound:.2e}")
+    assert bool((err <= bounds).all()), (op, label, e_k, e_t, bound)
 
 
 def exact(op, label, got, want):

@@ -6,8 +6,31 @@ import torch
 
 from oracle import cases as C
 from oracle import ref_sean as SN
+from tests import sean_checks as K
 
 pytestmark = pytest.mark.gpu
+
+
+def _dev():
+    if not torch.cuda.is_available():
+        pytest.fail("-m gpu tests need a GPU (torch.cuda.is_available() is False)")
+    return torch.device("cuda:0")
+
+
+@pytest.mark.parametrize("op,case", K.cases(gpu=True), ids=K.case_id)
+def test_sean_table_kernel(op, case):
+    """The label conv (both kernels, the wave vote of the per-pixel one on 64 real lanes) and both ACE tails called directly on
+    the hardware, against fp64 - tests/sean_checks.py."""
+    from hairfastgan_amd._runtime import lib, stream
+
+    K.CHECKS[op](lib(), stream(), _dev(), case)
+
+
+@pytest.mark.parametrize("op", K.BATCH_OPS)
+def test_sean_table_kernel_batch_invariance(op):
+    from hairfastgan_amd._runtime import lib, stream
+
+    K.check_batch_invariance(lib(), stream(), _dev(), op)
 
 
 def _model(dev):

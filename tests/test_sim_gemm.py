@@ -6,6 +6,20 @@ import torch
 import torch.nn.functional as F
 
 from hairfastgan_amd import _marshal as M
+from tests import gemm_checks as K
+
+CPU = torch.device("cpu")
+
+
+@pytest.mark.parametrize("op,case", K.cases(gpu=False), ids=K.case_id)
+def test_conv1x1_direct(simlib, op, case):
+    """Every tile form, stride, operand mode, epilogue, grouped and split-K form against the fp64 contract - tests/gemm_checks.py."""
+    K.CHECKS[op](simlib, None, CPU, case)
+
+
+@pytest.mark.parametrize("op", K.BATCH_OPS)
+def test_conv1x1_batch_invariance(simlib, op):
+    K.check_batch_invariance(simlib, None, CPU, op)
 
 
 def _prep(simlib, w):

@@ -12,6 +12,20 @@ from hairfastgan_amd import _marshal as M
 from oracle import cases as C
 from oracle import ref_sean as SN
 from oracle import synth
+from tests import sean_checks as K
+
+CPU = torch.device("cpu")
+
+
+@pytest.mark.parametrize("op,case", K.cases(gpu=False), ids=K.case_id)
+def test_sean_table_kernel(simlib, op, case):
+    """The label conv (both kernels, both paths of each, predicted bit for bit) and both ACE tails against fp64 - tests/sean_checks.py."""
+    K.CHECKS[op](simlib, None, CPU, case)
+
+
+@pytest.mark.parametrize("op", K.BATCH_OPS)
+def test_sean_table_kernel_batch_invariance(simlib, op):
+    K.check_batch_invariance(simlib, None, CPU, op)
 
 
 def test_oracle_reproduces_reference_codes(golden):
