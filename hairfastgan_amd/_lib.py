@@ -83,6 +83,13 @@ SIGNATURES = {
     "hf_jpeg_encode_u8": [_f, _ll, _f, _f, _i, _i, _i, _i, _i, _i, _f, _ll, _st],
     "hf_jpeg_decode_u8": [_f, _f, _f, _f, _ll, _f, _ll, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _ll, _st],
     "hf_png_decode_u8": [_f, _f, _f, _f, _ll, _f, _ll, _f, _i, _i, _i, _i, _i, _i, _f, _ll, _st],
+    "hf_frechet_accumulate_f64": [_f, _f, _f, _i, _i, _st],
+    "hf_frechet_accumulate_f16_f64": [_f, _f, _f, _i, _i, _st],
+    "hf_frechet_stats_f64": [_f, _f, _f, _f, _ll, _i, _st],
+    "hf_sym_eig_jacobi_f64": [_f, _f, _f, _f, _i, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double), _st],
+    "hf_sym_eig_jacobi_work_doubles": (_ll, [_i, _i]),
+    "hf_frechet_congruence_f64": [_f, _f, _f, _f, _f, _i, _st],
+    "hf_frechet_finish_f64": [_f, _f, _f, _f, _f, _f, _i, _st],
     "hf_maxpool3x3s2_f32":[_f, _f, _ll, _i, _i, _st],
     "hf_gate_f32": [_f, _f, _f, _f, _f, _fl, _ll, _i, _st],
     "hf_upsample_nearest_f32": [_f, _f, _ll, _i, _i, _i, _i, _st],

@@ -1606,3 +1606,89 @@ def png_decode(lib, st, streams, offsets, max_stream_bytes, palettes, h, w, colo
                                     int(max_stream_bytes), _p(palettes) if color_type == 3 else None, b, h, w, color_type, out_channels,
                                     int(token_cap), _p(ws), ws.numel() * 8, st), "hf_png_decode_u8")
     return out, outf, status
+
+
+# ---- Frechet distance (csrc/frechet.h; hairfastgan_amd.metrics chains these).  Everything fp64, row-major ----
+def _f64(t, shape, name):
+    if t.dtype != torch.float64 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous float64 tensor of shape {tuple(shape)}; got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def frechet_accumulate_into(lib, st, total, cov_sum, feats):
+    """total[d] += sum_n feats[n], cov_sum[d,d] += sum_n outer(feats[n], feats[n]) in fp64, samples in ascending n; feats
+    [n,d] fp32 or fp16 (upcast exactly)."""
+    if feats.ndim != 2 or feats.dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"features must be [n,d] float32 or float16; got {feats.dtype} {tuple(feats.shape)}")
+    n, d = feats.shape
+    _f64(total, (d,), "sum")
+    _f64(cov_sum, (d, d), "cov_sum")
+    if n == 0:
+        return
+    feats = feats if feats.is_contiguous() else feats.contiguous()
+    fn = lib.hf_frechet_accumulate_f64 if feats.dtype == torch.float32 else lib.hf_frechet_accumulate_f16_f64
+    check(lib, fn(_p(total), _p(cov_sum), _p(feats), n, d, st), fn.__name__)
+
+
+def frechet_stats(lib, st, total, cov_sum, n):
+    """(mu [d], cov [d,d]) = (sum / n, (cov_sum - n mu mu^T) / (n - 1))."""
+    d = total.numel()
+    _f64(total, (d,), "sum")
+    _f64(cov_sum, (d, d), "cov_sum")
+    mu, cov = torch.empty_like(total), torch.empty_like(cov_sum)
+    check(lib, lib.hf_frechet_stats_f64(_p(mu), _p(cov), _p(total), _p(cov_sum), int(n), d, st), "hf_frechet_stats_f64")
+    return mu, cov
+
+
+def sym_eigh_f64(lib, st, a, vectors=True, max_sweeps=30, info=None):
+    """Eigenvalues (in the solver's order) and, with `vectors`, eigenvectors (columns) of the symmetric fp64 matrix a [d,d]
+    by the Jacobi solver: (w [d], V [d,d] or None).  RuntimeError if `max_sweeps` sweeps do not converge.  `info`: a dict
+    that receives sweeps and off_norm.  Synchronises the stream once per sweep."""
+    import ctypes
+
+    if a.ndim != 2 or a.shape[0] != a.shape[1]:
+        raise ValueError(f"expected a square matrix; got {tuple(a.shape)}")
+    d = a.shape[0]
+    _f64(a, (d, d), "the matrix")
+    w = torch.empty(d, dtype=torch.float64, device=a.device)
+    v = torch.empty_like(a) if vectors else None
+    work = torch.empty(lib.hf_sym_eig_jacobi_work_doubles(d, 1 if vectors else 0), dtype=torch.float64, device=a.device)
+    sweeps, off = ctypes.c_int(0), ctypes.c_double(0.0)
+    check(lib, lib.hf_sym_eig_jacobi_f64(_p(w), _p(v), _p(a), _p(work), d, int(max_sweeps), ctypes.byref(sweeps), ctypes.byref(off), st),
+          "hf_sym_eig_jacobi_f64")
+    if info is not None:
+        info.update(sweeps=sweeps.value, off_norm=off.value)
+    if sweeps.value < 0:
+        raise RuntimeError(f"hf_sym_eig_jacobi_f64: no convergence in {max_sweeps} sweeps at d = {d} (off-diagonal norm {off.value:.3e})")
+    return w, v
+
+
+def frechet_congruence(lib, st, w, v, s2):
+    """B s2 B^T with B = diag(sqrt(max(w, 0))) v^T, symmetrised."""
+    d = w.numel()
+    _f64(w, (d,), "w")
+    _f64(v, (d, d), "V")
+    _f64(s2, (d, d), "sigma2")
+    out = torch.empty_like(s2)
+    work = torch.empty(2 * d * d, dtype=torch.float64, device=s2.device)
+    check(lib, lib.hf_frechet_congruence_f64(_p(out), _p(w), _p(v), _p(s2), _p(work), d, st), "hf_frechet_congruence_f64")
+    return out
+
+
+def frechet_distance_from_stats(lib, st, mu1, sigma1, mu2, sigma2, max_sweeps=30, info=None):
+    """|mu1 - mu2|^2 + tr(sigma1) + tr(sigma2) - 2 tr((sigma1 sigma2)^(1/2)) as a 0-d fp64 tensor on the device: the
+    spectrum of sigma1 sigma2 is taken from sigma1^(1/2) sigma2 sigma1^(1/2) (two symmetric eigenproblems)."""
+    if mu1.shape != mu2.shape or sigma1.shape != sigma2.shape:
+        raise ValueError(f"the two sides differ in dimension: {tuple(mu1.shape)} / {tuple(mu2.shape)}")
+    d = mu1.numel()
+    for t, shape, name in ((mu1, (d,), "mu1"), (mu2, (d,), "mu2"), (sigma1, (d, d), "sigma1"), (sigma2, (d, d), "sigma2")):
+        _f64(t, shape, name)
+    i1, i2 = {}, {}
+    w, v = sym_eigh_f64(lib, st, sigma1, True, max_sweeps, i1)
+    m = frechet_congruence(lib, st, w, v, sigma2)
+    ev, _ = sym_eigh_f64(lib, st, m, False, max_sweeps, i2)
+    if info is not None:
+        info.update(sweeps=(i1["sweeps"], i2["sweeps"]), off_norm=(i1["off_norm"], i2["off_norm"]))
+    out = torch.empty(1, dtype=torch.float64, device=mu1.device)
+    check(lib, lib.hf_frechet_finish_f64(_p(out), _p(mu1), _p(mu2), _p(sigma1), _p(sigma2), _p(ev), d, st), "hf_frechet_finish_f64")
+    return out.reshape(())

@@ -834,6 +834,38 @@ int hf_mha_small_f32(float *out, const float *qkv, int images, int seq, int head
 int hf_quick_gelu_f32(float *out, const float *x, long long n, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Frechet distance between feature sets (csrc/frechet.h; FID / FID-CLIP of scripts/fid_metric.py:25-50 and
+ * utils/train.py:90-161, which the reference leaves to torchmetrics and torch.linalg.eigvals).  Everything is fp64 and
+ * row-major; every double pointer must be 8-byte aligned (HF_E_INVALID otherwise, as for a null pointer or d <= 0).
+ * Results do not depend on the grid: each output has one owner thread, reductions are LDS trees of a fixed shape.
+ *
+ * hf_frechet_accumulate_f64: sum[j] += sum_n f[n][j], cov_sum[i][j] += sum_n f[n][i] f[n][j] for feats [n][d] (fp32; the
+ * _f16 form takes fp16 and upcasts exactly).  The owner of an element starts from the value in memory and adds the
+ * samples in ascending n, so k calls on consecutive slices give the bits of one call on the whole, and of the fp64
+ * loop `for n: cov += outer(f[n], f[n])`.  Both triangles are written: cov_sum is symmetric by construction. */
+int hf_frechet_accumulate_f64(double *sum, double *cov_sum, const float *feats, int n, int d, void *stream);
+int hf_frechet_accumulate_f16_f64(double *sum, double *cov_sum, const void *feats, int n, int d, void *stream);
+/* mu[d] = sum / n, cov[d][d] = (cov_sum - n (mu_i mu_j)) / (n - 1), every operation rounded once; n >= 2. */
+int hf_frechet_stats_f64(double *mu, double *cov, const double *sum, const double *cov_sum, long long n, int d, void *stream);
+/* Eigenvalues w[d] (in no particular order) and, unless v is NULL, eigenvectors (the columns of v[d][d], a = v diag(w) v^T)
+ * of the symmetric matrix a[d][d] (only read), by cyclic two-sided Jacobi in round-robin order: one launch per round over
+ * ping-pong buffers in `work` (hf_sym_eig_jacobi_work_doubles(d, v != NULL) doubles), d - 1 (d odd: d) launches per sweep; no
+ * kernel waits on another block.  A rotation is skipped when |a_pq| <= eps sqrt(|a_pp a_qq|).  After every sweep the host reads
+ * three doubles (this call synchronises `stream`; it cannot be captured into a graph) and stops when no pair is above
+ * that threshold or the off-diagonal Frobenius norm is <= eps |a|_F.  *sweeps = the sweeps run, or -1 when max_sweeps
+ * (>= 1) were run without convergence (w and v then hold the unconverged state); *off_norm = the last off-diagonal norm.
+ * sweeps and off_norm are host pointers.  d <= 16384. */
+int hf_sym_eig_jacobi_f64(double *w, double *v, const double *a, double *work, int d, int max_sweeps, int *sweeps, double *off_norm,
+                          void *stream);
+long long hf_sym_eig_jacobi_work_doubles(int d, int want_vectors);
+/* m_out[d][d] = B s2 B^T with B = diag(sqrt(max(w, 0))) v^T (w, v of hf_sym_eig_jacobi_f64: B^T B = the positive part of
+ * the decomposed matrix), two tiled fp64 products through work (2 d^2 doubles), stored as (M + M^T) / 2. */
+int hf_frechet_congruence_f64(double *m_out, const double *w, const double *v, const double *s2, double *work, int d, void *stream);
+/* out[0] = |mu1 - mu2|^2 + tr s1 + tr s2 - 2 sum_i sqrt(max(ev_i, 0)); not clamped at 0 (the reference does not). */
+int hf_frechet_finish_f64(double *out, const double *mu1, const double *mu2, const double *s1, const double *s2, const double *ev,
+                          int d, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Tuning / debugging hook (no reference counterpart): force the tile
  * configuration hf_modconv3x3_f32 / hf_modconv3x3_up_f32 dispatch to
  * (see the switch statements at the bottom of csrc/modconv.hip); 0 restores the
