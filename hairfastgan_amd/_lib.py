@@ -90,6 +90,12 @@ SIGNATURES = {
     "hf_sym_eig_jacobi_work_doubles": (_ll, [_i, _i]),
     "hf_frechet_congruence_f64": [_f, _f, _f, _f, _f, _i, _st],
     "hf_frechet_finish_f64": [_f, _f, _f, _f, _f, _f, _i, _st],
+    "hf_conv2d_direct_f32": [_f, _f, _f, _f, _f, _f, _i, _fl, _i, _i, _i, _i, _i, _i, _i, _i, _st],
+    "hf_maxpool2d_f32": [_f, _f, _ll, _i, _i, _i, _i, _st],
+    "hf_lpips_layer_f64": [_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _st],
+    "hf_lpips_layer_work_doubles": (_ll, [_i, _i, _i]),
+    "hf_sq_err_sum_f64": [_f, _f, _f, _f, _i, _ll, _i, _st],
+    "hf_sq_err_sum_work_doubles": (_ll, [_i, _ll]),
     "hf_maxpool3x3s2_f32":[_f, _f, _ll, _i, _i, _st],
     "hf_gate_f32": [_f, _f, _f, _f, _f, _fl, _ll, _i, _st],
     "hf_upsample_nearest_f32": [_f, _f, _ll, _i, _i, _i, _i, _st],

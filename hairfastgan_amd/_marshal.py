@@ -1692,3 +1692,55 @@ def frechet_distance_from_stats(lib, st, mu1, sigma1, mu2, sigma2, max_sweeps=30
     out = torch.empty(1, dtype=torch.float64, device=mu1.device)
     check(lib, lib.hf_frechet_finish_f64(_p(out), _p(mu1), _p(mu2), _p(sigma1), _p(sigma2), _p(ev), d, st), "hf_frechet_finish_f64")
     return out.reshape(())
+
+
+# ---- LPIPS and L2 / PSNR (csrc/lpips.h; hairfastgan_amd.lpips chains these) ----
+def conv2d_direct(lib, st, x, weight, stride=1, pad=0, in_scale=None, in_shift=None, bias=None, act=ACT_NONE, alpha=0.0):
+    """hf_conv2d_direct_f32: x [N,cin,H,W] (cin <= 4), weight [cout,cin,k,k] in torch's layout -> [N,cout,oh,ow]; the input
+    affine touches real pixels only (the padding stays zero)."""
+    x, weight = _c(x), _c(weight)
+    n, cin, h, w = x.shape
+    cout, cin_w, k, k2 = weight.shape
+    if cin_w != cin or k2 != k:
+        raise ValueError(f"weight {tuple(weight.shape)} does not fit an input of {cin} channels")
+    oh, ow = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    out = x.new_empty((n, cout, max(oh, 0), max(ow, 0)))
+    check(lib, lib.hf_conv2d_direct_f32(_p(out), _p(x), _p(weight), _p(_c(in_scale)), _p(_c(in_shift)), _p(_c(bias)), act,
+                                        float(alpha), n, cin, cout, h, w, k, stride, pad, st), "hf_conv2d_direct_f32")
+    return out
+
+
+def maxpool2d(lib, st, x, k, stride):
+    """nn.MaxPool2d(k, stride): no padding, floor mode."""
+    x = _c(x)
+    b, c, h, w = x.shape
+    out = x.new_empty((b, c, max((h - k) // stride + 1, 0), max((w - k) // stride + 1, 0)))
+    check(lib, lib.hf_maxpool2d_f32(_p(out), _p(x), b * c, h, w, k, stride, st), "hf_maxpool2d_f32")
+    return out
+
+
+def lpips_layer_into(lib, st, dist, fx, fy, lin_w, accumulate=False):
+    """dist [N] float64 = (or +=) the LPIPS distance of one layer's feature maps fx, fy [N,C,H,W] under lin_w [C]."""
+    fx, fy, lin_w = _c(fx), _c(fy), _c(lin_w).reshape(-1)
+    n, c, h, w = fx.shape
+    if fy.shape != fx.shape or lin_w.numel() != c:
+        raise ValueError(f"feature maps {tuple(fx.shape)} / {tuple(fy.shape)} and {lin_w.numel()} weights do not fit")
+    _f64(dist, (n,), "dist")
+    work = torch.empty(max(int(lib.hf_lpips_layer_work_doubles(n, h, w)), 1), dtype=torch.float64, device=fx.device)
+    check(lib, lib.hf_lpips_layer_f64(_p(dist), _p(fx), _p(fy), _p(lin_w), _p(work), n, c, h, w, 1 if accumulate else 0, st),
+          "hf_lpips_layer_f64")
+    return dist
+
+
+def sq_err_sum(lib, st, a, b):
+    """[N] float64: sum (a - b)^2 over everything but the first axis; a, b both uint8 or both fp32."""
+    if a.shape != b.shape or a.dtype != b.dtype or a.dtype not in (torch.uint8, torch.float32) or a.ndim < 2:
+        raise ValueError(f"two uint8 or two fp32 tensors [N, ...] of one shape; got {a.dtype} {tuple(a.shape)}, {b.dtype} {tuple(b.shape)}")
+    a, b = a.contiguous(), b.contiguous()
+    n = a.shape[0]
+    per_image = a.numel() // max(n, 1)
+    out = torch.empty(n, dtype=torch.float64, device=a.device)
+    work = torch.empty(max(int(lib.hf_sq_err_sum_work_doubles(n, per_image)), 1), dtype=torch.float64, device=a.device)
+    check(lib, lib.hf_sq_err_sum_f64(_p(out), _p(a), _p(b), _p(work), n, per_image, 1 if a.dtype == torch.uint8 else 0, st),
+          "hf_sq_err_sum_f64")
+    return out

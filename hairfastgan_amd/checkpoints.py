@@ -41,6 +41,8 @@ SHAPE_ADAPTOR_PATH = "pretrained_models/ShapeAdaptor/mask_generator.pth"        
 PP_LATENT_AVG_PATH = "pretrained_models/PostProcess/latent_avg.pt"                     # models/Encoders.py:112
 CLIP_CACHE = "~/.cache/clip"                                                            # clip.load's download_root default
 CLIP_FILES = {"ViT-B/32": "ViT-B-32.pt"}                                                # clip._MODELS basename
+TORCH_HUB_CACHE = "~/.cache/torch/hub/checkpoints"                                      # torch.hub's download cache
+LPIPS_TOWER_FILES = {"alex": "alexnet-owt-7be5be79.pth", "vgg": "vgg16-397923af.pth"}   # torchvision's model_urls basenames
 
 
 def resolve(path, root=None):
@@ -153,6 +155,25 @@ def clip_tower(name="ViT-B/32", root=None):
     except RuntimeError:  # not a TorchScript archive: a plain state dict
         obj = load_file(p, f"CLIP {name}")
         return obj.get("state_dict", obj) if isinstance(obj, dict) else obj.state_dict()
+
+
+def lpips_weights(net_type="alex", version="0.1", root=None):
+    """-> (torchvision `features.<i>.*` state dict, published `lin<j>.model.1.weight` state dict) of an LPIPS tower
+    (losses/pp_losses.py:446,457: models.alexnet(True) / models.vgg16(True); :474-486: the linear layers): the files
+    torch.hub keeps in its download cache.  HAIRFAST_LPIPS_TOWER / HAIRFAST_LPIPS_LIN name other files (INTEGRATION.md says
+    how to export them).  Nothing is downloaded."""
+    if net_type not in LPIPS_TOWER_FILES:
+        raise NotImplementedError(f"LPIPS net_type '{net_type}': the alex and vgg towers are built")
+    found = []
+    for env, name, what in (("HAIRFAST_LPIPS_TOWER", LPIPS_TOWER_FILES[net_type], f"torchvision {net_type} features"),
+                            ("HAIRFAST_LPIPS_LIN", f"{net_type}.pth", f"LPIPS v{version} linear layers ({net_type})")):
+        p = resolve(os.environ.get(env) or str(Path(TORCH_HUB_CACHE) / name), root)
+        if not p.is_file():
+            raise FileNotFoundError(f"{what}: '{p}' not found; nothing is downloaded here - set {env} to the exported state dict")
+        obj = load_file(p, what)
+        found.append(obj.get("state_dict", obj) if isinstance(obj, dict) else obj.state_dict())
+    tower = {k: v for k, v in found[0].items() if k.startswith("features.")}
+    return tower, found[1]
 
 
 def blending(path, root=None, need_tower=True):

@@ -31,6 +31,7 @@
 #include "jpeg_decode.h"
 #include "png_decode.h"
 #include "frechet.h"
+#include "lpips.h"
 
 // Floating-point contraction: "on" = a multiply and an add are fused only where they are written in ONE expression (or as
 // fmaf), never across statements.  hipcc's default ("fast") lets the backend fuse opportunistically per basic block: the

@@ -48,17 +48,29 @@ USE_FUSED = None
 def lanczos_coeffs(in_size, out_size):
     """Tables of one Lanczos pass in_size -> out_size: (bounds int32 [out,2] = (first tap, tap count), kk int32
     [out,ksize] fixed-point weights).  All rows at once; a row's weights are summed in tap order (cumsum), as Pillow does."""
+    return _filter_coeffs(in_size, out_size, LANCZOS_SUPPORT,
+                          lambda t: np.where((t >= -3.0) & (t < 3.0), _sinc(t) * _sinc(t / 3.0), 0.0))
+
+
+@functools.lru_cache(maxsize=32)
+def bilinear_coeffs(in_size, out_size):
+    """The same tables for Pillow's BILINEAR (triangle) filter, support 1: hf_resize_lanczos_u8 takes host tables and does
+    not know its filter, so `Image.resize(size, BILINEAR)` is the same kernel with these."""
+    return _filter_coeffs(in_size, out_size, 1.0, lambda t: np.where(np.abs(t) < 1.0, 1.0 - np.abs(t), 0.0))
+
+
+def _filter_coeffs(in_size, out_size, filter_support, weight):
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for a filter of the given support; weight(t) -> filter values."""
     scale = in_size / out_size
     fs = max(scale, 1.0)
-    support = LANCZOS_SUPPORT * fs
+    support = filter_support * fs
     ksize = int(np.ceil(support)) * 2 + 1
     center = (np.arange(out_size) + 0.5) * scale
     first = np.maximum((center - support + 0.5).astype(np.int64), 0)              # C's (int): truncation
     count = np.minimum((center + support + 0.5).astype(np.int64), in_size) - first
     tap = np.arange(ksize)[None, :]
     t = ((tap + first[:, None]) - center[:, None] + 0.5) * (1.0 / fs)
-    live = (tap < count[:, None]) & (t >= -3.0) & (t < 3.0)
-    w = np.where(live, _sinc(t) * _sinc(t / 3.0), 0.0)
+    w = np.where(tap < count[:, None], weight(t), 0.0)
     total = np.cumsum(w, axis=1)[:, -1:]                                          # + 0.0 for the dead taps changes nothing
     w = np.where(total != 0.0, w / np.where(total != 0.0, total, 1.0), w)
     q = np.where(w < 0, w * (1 << PRECISION_BITS) - 0.5, w * (1 << PRECISION_BITS) + 0.5).astype(np.int64)
@@ -195,19 +207,24 @@ def alignment_plan(lm, width, height, output_size=1024, transform_size=4096, ena
 # device stages
 # ---------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=32)
-def _device_coeffs(in_size, out_size, device):
-    bounds, kk = lanczos_coeffs(in_size, out_size)
+def _device_coeffs(in_size, out_size, device, coeffs=lanczos_coeffs):
+    bounds, kk = coeffs(in_size, out_size)
     return torch.from_numpy(bounds).to(device), torch.from_numpy(kk).to(device)
 
 
-def resize_lanczos(L, st, img, out_w, out_h):
+def resize_lanczos(L, st, img, out_w, out_h, coeffs=lanczos_coeffs):
     """PIL Image.resize((out_w, out_h), LANCZOS) of planar uint8 [C,H,W]."""
     h, w = img.shape[-2:]
     if (out_h, out_w) == (h, w):
         return img.clone()
-    tx = _device_coeffs(w, out_w, img.device) if out_w != w else None
-    ty = _device_coeffs(h, out_h, img.device) if out_h != h else None
+    tx = _device_coeffs(w, out_w, img.device, coeffs) if out_w != w else None
+    ty = _device_coeffs(h, out_h, img.device, coeffs) if out_h != h else None
     return M.resize_lanczos_u8(L, st, img, out_h, out_w, tx, ty)
+
+
+def resize_bilinear(L, st, img, out_w, out_h):
+    """PIL Image.resize((out_w, out_h), BILINEAR) of planar uint8 [C,H,W]."""
+    return resize_lanczos(L, st, img, out_w, out_h, bilinear_coeffs)
 
 
 def quad_transform(L, st, img, quad, size):

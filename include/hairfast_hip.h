@@ -866,6 +866,35 @@ int hf_frechet_finish_f64(double *out, const double *mu1, const double *mu2, con
                           int d, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * Reconstruction metrics: LPIPS and L2 / PSNR (csrc/lpips.h; losses/pp_losses.py:375-529,
+ * models/encoder4editing/scripts/calc_losses_on_images.py).  Plain stores, no atomics, one owner per output element and a
+ * fixed order of every sum: a sample's bits depend neither on the batch size nor on its position in the batch.
+ *
+ * hf_conv2d_direct_f32: y = act(conv_{k x k, stride, pad}(in_scale[ci] x + in_shift[ci]) + bias[co]) for an input with few
+ * channels, in exact fp32 FMA: x [n,cin,h,w], weight [cout,cin,k,k] (torch's layout), y [n,cout,oh,ow] with
+ * oh = (h + 2 pad - k) / stride + 1 (floored).  The affine (either pointer may be NULL: scale 1 / shift 0) is applied to real
+ * pixels only, the padding stays zero: a z-score followed by a zero-padded conv.  Products are summed in ascending
+ * (ci, ky, kx); bias may be NULL; act = 0 (none) or 1 (leaky ReLU with slope alpha; alpha 0 = ReLU).
+ * cin <= 4, k <= 11, stride 1..4, 0 <= pad < k, any cout; anything else returns HF_E_INVALID. */
+int hf_conv2d_direct_f32(float *out, const float *x, const float *weight, const float *in_scale, const float *in_shift,
+                         const float *bias, int act, float alpha, int n, int cin, int cout, int h, int w, int k, int stride, int pad,
+                         void *stream);
+/* nn.MaxPool2d(k, stride) without padding, floor mode, on [planes, h, w] -> [planes, (h-k)/stride+1, (w-k)/stride+1];
+ * k = 2 or 3, 1 <= stride <= k, h, w >= k.  (hf_maxpool3x3s2_f32 is the padded ResNet form.) */
+int hf_maxpool2d_f32(float *out, const float *x, long long planes, int h, int w, int k, int stride, void *stream);
+/* One LPIPS layer (pp_losses.py:469-471, 520-526): fx, fy [n,c,h,w] fp32, lin_w [c];
+ *   dist[i] = (or +=, accumulate != 0) 1/(h w) sum_pixels sum_c lin_w[c] (fx_c / (|fx| + 1e-10) - fy_c / (|fy| + 1e-10))^2
+ * with |.| the channel norm at the pixel.  Per-pixel arithmetic is fp32 and forms the normalised difference itself (equal
+ * inputs give exactly 0), sums across pixels are fp64.  work: hf_lpips_layer_work_doubles(n, h, w) doubles. */
+int hf_lpips_layer_f64(double *dist, const float *fx, const float *fy, const float *lin_w, double *work, int n, int c, int h, int w,
+                       int accumulate, void *stream);
+long long hf_lpips_layer_work_doubles(int n, int h, int w);
+/* out[i] = sum_e (a[i][e] - b[i][e])^2 in fp64 over per_image elements; a, b uint8 (is_u8 != 0: the sum is an exact
+ * integer) or fp32.  work: hf_sq_err_sum_work_doubles(n, per_image) doubles (block partials, added in a fixed order). */
+int hf_sq_err_sum_f64(double *out, const void *a, const void *b, double *work, int n, long long per_image, int is_u8, void *stream);
+long long hf_sq_err_sum_work_doubles(int n, long long per_image);
+
+/* ---------------------------------------------------------------------------
  * Tuning / debugging hook (no reference counterpart): force the tile
  * configuration hf_modconv3x3_f32 / hf_modconv3x3_up_f32 dispatch to
  * (see the switch statements at the bottom of csrc/modconv.hip); 0 restores the
