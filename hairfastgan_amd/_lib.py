@@ -96,6 +96,9 @@ SIGNATURES = {
     "hf_lpips_layer_work_doubles": (_ll, [_i, _i, _i]),
     "hf_sq_err_sum_f64": [_f, _f, _f, _f, _i, _ll, _i, _st],
     "hf_sq_err_sum_work_doubles": (_ll, [_i, _ll]),
+    "hf_crop_avgpool_f32": [_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _st],
+    "hf_l2_normalize_rows_f32": [_f, _f, _f, _i, _i, _st],
+    "hf_row_similarity_f64": [_f, _f, _f, _i, _i, _i, _i, _st],
     "hf_maxpool3x3s2_f32":[_f, _f, _ll, _i, _i, _st],
     "hf_gate_f32": [_f, _f, _f, _f, _f, _fl, _ll, _i, _st],
     "hf_upsample_nearest_f32": [_f, _f, _ll, _i, _i, _i, _i, _st],

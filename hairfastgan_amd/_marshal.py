@@ -1744,3 +1744,36 @@ def sq_err_sum(lib, st, a, b):
     check(lib, lib.hf_sq_err_sum_f64(_p(out), _p(a), _p(b), _p(work), n, per_image, 1 if a.dtype == torch.uint8 else 0, st),
           "hf_sq_err_sum_f64")
     return out
+
+
+# ---- identity similarity (csrc/identity.h; hairfastgan_amd.identity chains these) ----
+def crop_avgpool(lib, st, x, y0, x0, ch, cw, oh, ow, scale=None, shift=None):
+    """hf_crop_avgpool_f32: AdaptiveAvgPool2d((oh, ow)) of x[:, :, y0:y0+ch, x0:x0+cw], the window read in place;
+    scale / shift [C]: a per-channel affine of the means."""
+    x = _c(x)
+    n, c, h, w = x.shape
+    out = x.new_empty((n, c, max(oh, 0), max(ow, 0)))
+    check(lib, lib.hf_crop_avgpool_f32(_p(out), _p(x), _p(_c(scale)), _p(_c(shift)), n, c, h, w, y0, x0, ch, cw, oh, ow, st),
+          "hf_crop_avgpool_f32")
+    return out
+
+
+def l2_normalize_rows(lib, st, x, want_norms=False):
+    """hf_l2_normalize_rows_f32: x [R,D] -> x / |x|_2 per row (-> (unit rows, norms [R]) with want_norms)."""
+    x = _c(x)
+    rows, d = x.shape
+    out = torch.empty_like(x)
+    norms = x.new_empty(rows) if want_norms else None
+    check(lib, lib.hf_l2_normalize_rows_f32(_p(out), _p(norms), _p(x), rows, d, st), "hf_l2_normalize_rows_f32")
+    return (out, norms) if want_norms else out
+
+
+def row_similarity(lib, st, a, b, paired=True):
+    """hf_row_similarity_f64: fp32 rows a [N,D], b [M,D] -> float64 [N] (paired, N == M) or [N,M]."""
+    a, b = _c(a), _c(b)
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1] or (paired and a.shape[0] != b.shape[0]):
+        raise ValueError(f"rows {tuple(a.shape)} and {tuple(b.shape)} do not fit{' pairwise' if paired else ''}")
+    n, m = a.shape[0], b.shape[0]
+    out = torch.empty((n,) if paired else (n, m), dtype=torch.float64, device=a.device)
+    check(lib, lib.hf_row_similarity_f64(_p(out), _p(a), _p(b), n, m, a.shape[1], 1 if paired else 0, st), "hf_row_similarity_f64")
+    return out

@@ -14,6 +14,7 @@ to the working directory (a HairFastGAN checkout with `pretrained_models/` downl
 | RotateModel | args.rotate_checkpoint | ['model_state_dict'] | models/Alignment.py:36-38 |
 | ClipBlendingModel | args.blending_checkpoint | ['model_state_dict'] (strict=False), ['clip'] names the tower (default ViT-B/32) | models/Blending.py:24-27 |
 | CLIP ViT-B/32 | the blending checkpoint's `clip_model.*` entries when it carries them (they overwrite clip.load's weights in the reference's load_state_dict), else clip.load's download cache ~/.cache/clip/ViT-B-32.pt (a TorchScript archive) | `visual.*` | models/Encoders.py:79; requirements.txt:6 |
+| ArcFace IR-SE50 (identity metric) | pretrained_models/ArcFace/ir_se50.pth, else e4e's pretrained_models/model_ir_se50.pth | plain | losses/pp_losses.py:271-274, encoder4editing/criteria/id_loss.py:11-12 |
 | PostProcessModel | args.pp_checkpoint ['model_state_dict'] + pretrained_models/PostProcess/latent_avg.pt | | models/Blending.py:29-30, models/Encoders.py:112 |
 
 A file that does not exist raises FileNotFoundError naming it and the network it holds: nothing here ever falls back to
@@ -42,6 +43,8 @@ PP_LATENT_AVG_PATH = "pretrained_models/PostProcess/latent_avg.pt"              
 CLIP_CACHE = "~/.cache/clip"                                                            # clip.load's download_root default
 CLIP_FILES = {"ViT-B/32": "ViT-B-32.pt"}                                                # clip._MODELS basename
 TORCH_HUB_CACHE = "~/.cache/torch/hub/checkpoints"                                      # torch.hub's download cache
+ARCFACE_PATH = "pretrained_models/ArcFace/ir_se50.pth"                                 # DefaultPaths.ir_se50_path (pp_losses.py:274)
+ARCFACE_E4E_PATH = "pretrained_models/model_ir_se50.pth"                                # e4e's configs/paths_config.py 'ir_se50'
 LPIPS_TOWER_FILES = {"alex": "alexnet-owt-7be5be79.pth", "vgg": "vgg16-397923af.pth"}   # torchvision's model_urls basenames
 
 
@@ -174,6 +177,21 @@ def lpips_weights(net_type="alex", version="0.1", root=None):
         found.append(obj.get("state_dict", obj) if isinstance(obj, dict) else obj.state_dict())
     tower = {k: v for k, v in found[0].items() if k.startswith("features.")}
     return tower, found[1]
+
+
+def arcface(root=None, path=ARCFACE_PATH):
+    """-> the state dict of the ArcFace IR-SE50 `Backbone(112, 50, mode="ir_se")` (pp_losses.py:271-274): `path`, else the
+    place e4e's own checkout keeps the same file.  Nothing is downloaded."""
+    tried = []
+    for cand in (path, ARCFACE_E4E_PATH):
+        p = resolve(cand, root)
+        if p.is_file():
+            obj = load_file(p, "ArcFace IR-SE50 (pp_losses.py:274)")
+            return obj.get("state_dict", obj) if isinstance(obj, dict) else obj.state_dict()
+        if str(p) not in tried:
+            tried.append(str(p))
+    raise FileNotFoundError("ArcFace IR-SE50 (losses/pp_losses.py:274 ir_se50.pth): none of " + ", ".join(f"'{t}'" for t in tried) +
+                            " found; nothing is downloaded here - pass --weights / path= or set HAIRFAST_PRETRAINED_ROOT")
 
 
 def blending(path, root=None, need_tower=True):

@@ -32,6 +32,7 @@
 #include "png_decode.h"
 #include "frechet.h"
 #include "lpips.h"
+#include "identity.h"
 
 // Floating-point contraction: "on" = a multiply and an add are fused only where they are written in ONE expression (or as
 // fmaf), never across statements.  hipcc's default ("fast") lets the backend fuse opportunistically per basic block: the

@@ -895,6 +895,26 @@ int hf_sq_err_sum_f64(double *out, const void *a, const void *b, double *work, i
 long long hf_sq_err_sum_work_doubles(int n, long long per_image);
 
 /* ---------------------------------------------------------------------------
+ * Identity similarity (csrc/identity.h; ArcFace IR-SE50 `IDLoss`, losses/pp_losses.py:267-296 and
+ * models/encoder4editing/criteria/id_loss.py): what stands around the network's body.  One owner per output element, every
+ * sum in a fixed order: an image's, a row's or an entry's bits do not depend on what else the launch holds.
+ *
+ * hf_crop_avgpool_f32: out [n,c,oh,ow] = AdaptiveAvgPool2d((oh, ow)) of the window x[:, :, y0:y0+ch, x0:x0+cw] of the
+ * contiguous x [n,c,h,w], read in place.  Bin i covers the window's rows floor(i ch / oh) .. ceil((i + 1) ch / oh) - 1
+ * (columns likewise); its pixels are added in fp32 in row-major order and the sum is divided by the count.  scale / shift
+ * [c] (either may be NULL: 1 / 0): out = fmaf(scale[c], mean, shift[c]).  One lane per output element: meant for windows of
+ * a few pixels (hf_adaptive_avgpool_f32 spends a wave per bin).  A window that leaves the image or a non-positive size
+ * returns HF_E_INVALID. */
+int hf_crop_avgpool_f32(float *out, const float *x, const float *scale, const float *shift, int n, int c, int h, int w, int y0,
+                        int x0, int ch, int cw, int oh, int ow, void *stream);
+/* out[r][:] = x[r][:] / norm_r, norm_r = fp32(sqrt(sum_k x[r][k]^2)) with the sum in fp64 (pp_losses.py:50-53 l2_norm; a zero
+ * row gives NaN as torch.div does); norms [rows] receives norm_r unless NULL. */
+int hf_l2_normalize_rows_f32(float *out, float *norms, const float *x, int rows, int d, void *stream);
+/* a [n,d], b [m,d] fp32.  paired != 0 (n == m): out[i] = a[i] . b[i]; else out[i][j] = a[i] . b[j] ([n,m]).  Products and
+ * sums are fp64 in an order that depends on d alone: out[i] of the paired form and out[i][i] of the matrix have equal bits. */
+int hf_row_similarity_f64(double *out, const float *a, const float *b, int n, int m, int d, int paired, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Tuning / debugging hook (no reference counterpart): force the tile
  * configuration hf_modconv3x3_f32 / hf_modconv3x3_up_f32 dispatch to
  * (see the switch statements at the bottom of csrc/modconv.hip); 0 restores the
