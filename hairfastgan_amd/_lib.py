@@ -99,6 +99,9 @@ SIGNATURES = {
     "hf_crop_avgpool_f32": [_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _st],
     "hf_l2_normalize_rows_f32": [_f, _f, _f, _i, _i, _st],
     "hf_row_similarity_f64": [_f, _f, _f, _i, _i, _i, _i, _st],
+    "hf_conv2d_rect_f16_f32": [_f, _f, _f, _f, _f, _i, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _st],
+    "hf_pool3x3_f32": [_f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _st],
+    "hf_resize_bilinear_tf1_f32": [_f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _fl, _fl, _st],
     "hf_maxpool3x3s2_f32":[_f, _f, _ll, _i, _i, _st],
     "hf_gate_f32": [_f, _f, _f, _f, _f, _fl, _ll, _i, _st],
     "hf_upsample_nearest_f32": [_f, _f, _ll, _i, _i, _i, _i, _st],

@@ -1777,3 +1777,69 @@ def row_similarity(lib, st, a, b, paired=True):
     out = torch.empty((n,) if paired else (n, m), dtype=torch.float64, device=a.device)
     check(lib, lib.hf_row_similarity_f64(_p(out), _p(a), _p(b), n, m, a.shape[1], 1 if paired else 0, st), "hf_row_similarity_f64")
     return out
+
+
+# ---- FID Inception-v3 (csrc/conv_rect.h, csrc/inception.h; hairfastgan_amd.inception chains these) ----
+class RectWeights:
+    """A rectangular conv's weights prepared once: `w` [cout,cin,kh,kw] fp32 (the exact-fp32 form reads it) and, derived on
+    first use, the fp16 (hi, lo) split of the zero-padded table [tap*cinp + ci][co] for the matrix-core form."""
+
+    def __init__(self, w):
+        self.w = _c(w.detach())
+        self.cout, self.cin, self.kh, self.kw = self.w.shape
+        self._f16 = None
+
+    def f16(self, lib, st):
+        if self._f16 is None:
+            cinp, coutp = -(-self.cin // 32) * 32, -(-self.cout // 64) * 64
+            table = self.w.new_zeros((self.kh * self.kw, cinp, coutp))
+            table[:, :self.cin, :self.cout] = self.w.permute(2, 3, 1, 0).reshape(self.kh * self.kw, self.cin, self.cout)
+            self._f16 = conv_split_weights_f16(lib, st, table.reshape(1, -1, coutp))
+        return self._f16
+
+
+def conv_out_size(size, k, stride, pad):
+    return (size + 2 * pad - k) // stride + 1
+
+
+def conv2d_rect_into(lib, st, out, oc0, x, xc0, wts, nterms, stride=1, pad=(0, 0), out_scale=None, bias=None, relu=False):
+    """hf_conv2d_rect_f16_f32: channels oc0 .. oc0+cout-1 of out [N,Co,oh,ow] = the conv of channels xc0 .. xc0+cin-1 of
+    x [N,Cx,H,W] with `wts` (a RectWeights), torch's symmetric padding pad = (rows, columns); nterms 3 / 1 / 0."""
+    if x.dtype != torch.float32 or out.dtype != torch.float32 or not x.is_contiguous() or not out.is_contiguous():
+        raise TypeError("conv2d_rect_into takes contiguous fp32 tensors")
+    n, xct, h, w = x.shape
+    oh, ow = conv_out_size(h, wts.kh, stride, pad[0]), conv_out_size(w, wts.kw, stride, pad[1])
+    if out.ndim != 4 or out.shape[0] != n or out.shape[2] != oh or out.shape[3] != ow or oc0 < 0 or oc0 + wts.cout > out.shape[1]:
+        raise ValueError(f"output {tuple(out.shape)} does not hold channels {oc0}..{oc0 + wts.cout - 1} of [{n},*,{oh},{ow}]")
+    hi, lo = wts.f16(lib, st) if nterms else (None, None)
+    check(lib, lib.hf_conv2d_rect_f16_f32(_p(out), _p(x), _p(wts.w), _p(hi), _p(lo), nterms, _p(_c(out_scale)), _p(_c(bias)),
+                                          1 if relu else 0, n, wts.cin, wts.cout, h, w, wts.kh, wts.kw, stride, pad[0], pad[1], oh, ow,
+                                          xc0, xct, oc0, out.shape[1], st), "hf_conv2d_rect_f16_f32")
+    return out
+
+
+def pool3x3_into(lib, st, out, oc0, x, xc0, c, mode, stride):
+    """hf_pool3x3_f32: mode "max" / "avg" (padding not counted); stride 1 (pad 1) or 2 (pad 0, floor)."""
+    if x.dtype != torch.float32 or out.dtype != torch.float32 or not x.is_contiguous() or not out.is_contiguous():
+        raise TypeError("pool3x3_into takes contiguous fp32 tensors")
+    n, xct, h, w = x.shape
+    oh, ow = (h, w) if stride == 1 else ((h - 3) // 2 + 1, (w - 3) // 2 + 1)
+    if out.ndim != 4 or out.shape[0] != n or out.shape[2] != oh or out.shape[3] != ow or oc0 < 0 or oc0 + c > out.shape[1]:
+        raise ValueError(f"output {tuple(out.shape)} does not hold channels {oc0}..{oc0 + c - 1} of [{n},*,{oh},{ow}]")
+    check(lib, lib.hf_pool3x3_f32(_p(out), _p(x), {"max": 0, "avg": 1}[mode], n, c, h, w, stride, xc0, xct, oc0, out.shape[1], st),
+          "hf_pool3x3_f32")
+    return out
+
+
+def resize_bilinear_tf1(lib, st, x, oh, ow, mul=None, add=None):
+    """hf_resize_bilinear_tf1_f32: x [N,C,H,W] uint8 or fp32 -> fp32 [N,C,oh,ow]; mul / add: v * mul + add of the result."""
+    if x.dtype not in (torch.uint8, torch.float32) or x.ndim != 4:
+        raise TypeError(f"resize_bilinear_tf1 takes uint8 or fp32 [N,C,H,W]; got {x.dtype} {tuple(x.shape)}")
+    x = x.contiguous()
+    n, c, h, w = x.shape
+    out = torch.empty((n, c, oh, ow), dtype=torch.float32, device=x.device)
+    affine = mul is not None or add is not None
+    check(lib, lib.hf_resize_bilinear_tf1_f32(_p(out), _p(x), 1 if x.dtype == torch.uint8 else 0, n, c, h, w, oh, ow, 1 if affine else 0,
+                                              1.0 if mul is None else float(mul), 0.0 if add is None else float(add), st),
+          "hf_resize_bilinear_tf1_f32")
+    return out

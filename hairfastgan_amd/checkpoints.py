@@ -15,6 +15,7 @@ to the working directory (a HairFastGAN checkout with `pretrained_models/` downl
 | ClipBlendingModel | args.blending_checkpoint | ['model_state_dict'] (strict=False), ['clip'] names the tower (default ViT-B/32) | models/Blending.py:24-27 |
 | CLIP ViT-B/32 | the blending checkpoint's `clip_model.*` entries when it carries them (they overwrite clip.load's weights in the reference's load_state_dict), else clip.load's download cache ~/.cache/clip/ViT-B-32.pt (a TorchScript archive) | `visual.*` | models/Encoders.py:79; requirements.txt:6 |
 | ArcFace IR-SE50 (identity metric) | pretrained_models/ArcFace/ir_se50.pth, else e4e's pretrained_models/model_ir_se50.pth | plain | losses/pp_losses.py:271-274, encoder4editing/criteria/id_loss.py:11-12 |
+| FID Inception-v3 (the plain FID column) | HAIRFAST_INCEPTION_WEIGHTS, else pt_inception-2015-12-05-6726825d.pth in torch's hub cache (the basename is stated from memory of torch-fidelity) | plain; `fc.*` unused | scripts/fid_metric.py:30 (torchmetrics' FrechetInceptionDistance) |
 | PostProcessModel | args.pp_checkpoint ['model_state_dict'] + pretrained_models/PostProcess/latent_avg.pt | | models/Blending.py:29-30, models/Encoders.py:112 |
 
 A file that does not exist raises FileNotFoundError naming it and the network it holds: nothing here ever falls back to
@@ -45,6 +46,8 @@ CLIP_FILES = {"ViT-B/32": "ViT-B-32.pt"}                                        
 TORCH_HUB_CACHE = "~/.cache/torch/hub/checkpoints"                                      # torch.hub's download cache
 ARCFACE_PATH = "pretrained_models/ArcFace/ir_se50.pth"                                 # DefaultPaths.ir_se50_path (pp_losses.py:274)
 ARCFACE_E4E_PATH = "pretrained_models/model_ir_se50.pth"                                # e4e's configs/paths_config.py 'ir_se50'
+# torch-fidelity's URL_INCEPTION_V3 basename - stated from memory, not checked against an installed torch-fidelity
+INCEPTION_FID_FILE = "pt_inception-2015-12-05-6726825d.pth"
 LPIPS_TOWER_FILES = {"alex": "alexnet-owt-7be5be79.pth", "vgg": "vgg16-397923af.pth"}   # torchvision's model_urls basenames
 
 
@@ -192,6 +195,19 @@ def arcface(root=None, path=ARCFACE_PATH):
             tried.append(str(p))
     raise FileNotFoundError("ArcFace IR-SE50 (losses/pp_losses.py:274 ir_se50.pth): none of " + ", ".join(f"'{t}'" for t in tried) +
                             " found; nothing is downloaded here - pass --weights / path= or set HAIRFAST_PRETRAINED_ROOT")
+
+
+def inception_fid(root=None, path=None):
+    """-> the state dict of the FID Inception-v3 (hairfastgan_amd.inception.InceptionV3): `path`, else the file
+    HAIRFAST_INCEPTION_WEIGHTS names, else INCEPTION_FID_FILE in torch's hub cache, where torch-fidelity (and with it
+    torchmetrics) leaves it.  Nothing is downloaded."""
+    what = "FID Inception-v3 (torchmetrics' FrechetInceptionDistance, scripts/fid_metric.py)"
+    p = resolve(path or os.environ.get("HAIRFAST_INCEPTION_WEIGHTS") or str(Path(TORCH_HUB_CACHE) / INCEPTION_FID_FILE), root)
+    if not p.is_file():
+        raise FileNotFoundError(f"{what}: '{p}' not found; nothing is downloaded here - pass --inception_weights / path= or set "
+                                "HAIRFAST_INCEPTION_WEIGHTS")
+    obj = load_file(p, what)
+    return obj.get("state_dict", obj) if isinstance(obj, dict) else obj.state_dict()
 
 
 def blending(path, root=None, need_tower=True):

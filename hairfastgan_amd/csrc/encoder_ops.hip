@@ -33,6 +33,7 @@
 #include "frechet.h"
 #include "lpips.h"
 #include "identity.h"
+#include "inception.h"
 
 // Floating-point contraction: "on" = a multiply and an add are fused only where they are written in ONE expression (or as
 // fmaf), never across statements.  hipcc's default ("fast") lets the backend fuse opportunistically per basic block: the

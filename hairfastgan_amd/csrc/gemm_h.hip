@@ -719,4 +719,6 @@ extern "C" int hf_modconv3x3_small_up_blur_f16_f32(float *out, void *out_hi, voi
   return hf_launch_status();
 }
 
+#include "conv_rect.h"  // hf_conv2d_rect_f16_f32: the tap-rectangle convolution between channel slices
+
 extern "C" unsigned long long hf_f16_overflow_count_gemm(int reset) { return hf_f16_overflow_read_tu(reset); }

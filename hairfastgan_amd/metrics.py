@@ -11,7 +11,8 @@ Pieces, all on the library's kernels:
   statistics -> distance            `FrechetDistance.compute`: hf_frechet_stats_f64, two Jacobi eigensolves
                                     (hf_sym_eig_jacobi_f64) around hf_frechet_congruence_f64, hf_frechet_finish_f64
 The host lists files and copies one double per method back.  The Inception-v3 half of fid_metric.py (the plain `FID` column)
-is not part of this backend: that network is not built here and there are no weights for it.
+is `FrechetDistance(hairfastgan_amd.inception.InceptionV3(2048, weights=...))`, the command line's --fid; its weights are an
+explicit argument (`checkpoints.inception_fid()` finds the published file), never an implicit download.
 
 Every entry point takes `lib=None`: the loaded HIP library on torch's current stream.  Tests hand in the CPU interpreter
 build of the same kernel sources and CPU tensors.
@@ -74,8 +75,9 @@ class ClipModel:
 class FrechetDistance:
     """The call surface of torchmetrics' FrechetInceptionDistance as scripts/fid_metric.py uses it, on the device.
 
-    feature: a callable images -> features [N,d] (fp32 or fp16), e.g. `ClipModel()`.  An int (torchmetrics' Inception-v3
-        layer widths 64 / 192 / 768 / 2048) raises NotImplementedError: that network is not part of this backend.
+    feature: a callable images -> features [N,d] (fp32 or fp16), e.g. `ClipModel()` or `inception.InceptionV3(2048, weights)`.
+        An int (torchmetrics' Inception-v3 layer widths 64 / 192 / 768 / 2048) raises NotImplementedError: torchmetrics then
+        downloads weights, here they are an explicit argument of the module.
     reset_real_features: False keeps the statistics of the real side over `reset()`.
     normalize: accepted for signature compatibility and WITHOUT effect: in torchmetrics it only rescales [0,1] float
         images to bytes in front of the built-in Inception network and is not applied with a feature module - stated
@@ -89,8 +91,9 @@ class FrechetDistance:
     def __init__(self, feature, reset_real_features=True, normalize=False, max_sweeps=30, lib=None):
         if isinstance(feature, int):
             raise NotImplementedError(
-                f"feature={feature}: the Inception-v3 feature extractor is not part of this backend (no network, no weights); "
-                "pass a feature module such as hairfastgan_amd.metrics.ClipModel()")
+                f"feature={feature}: an integer would need the Inception-v3 weights downloaded implicitly; pass the module with its "
+                f"weights, FrechetDistance(InceptionV3({feature}, weights=checkpoints.inception_fid())) from hairfastgan_amd.inception, "
+                "or another feature module such as hairfastgan_amd.metrics.ClipModel()")
         if not callable(feature):
             raise TypeError("feature must be a callable images -> [N,d]")
         self.feature = feature
@@ -222,15 +225,20 @@ def _name_path(pair):
     return name, Path(path)
 
 
-def main(argv=None, feature=None, lib=None, device=None):
-    """The command line of scripts/fid_metric.py, FID_CLIP column only.  `feature`: the feature module (default
-    `ClipModel()`)."""
-    parser = argparse.ArgumentParser(prog="python -m hairfastgan_amd.metrics", description="Compute FID-CLIP")
+def main(argv=None, feature=None, lib=None, device=None, inception=None):
+    """The command line of scripts/fid_metric.py: the FID_CLIP column and, with --fid, the plain FID column in front of it (the
+    reference's order).  `feature`: the FID_CLIP feature module (default `ClipModel()`); `inception`: the FID one (default
+    `InceptionV3(2048)` with the weights of --inception_weights or of `checkpoints.inception_fid`).
+    -> {method: FID_CLIP}, with --fid {"FID": {method: value}, "FID_CLIP": {method: value}}."""
+    parser = argparse.ArgumentParser(prog="python -m hairfastgan_amd.metrics", description="Compute FID-CLIP (and FID)")
     parser.add_argument("--source_dataset", type=Path, required=True, help="Dataset with real faces")
     parser.add_argument("--methods_dataset", type=_name_path, nargs="+", required=True, help="name,DIR of each method's results")
     parser.add_argument("--output", type=Path, default=Path("logs/metric.csv"), help="the CSV file to write")
     parser.add_argument("--image_decoder", choices=("pil", "device"), default="pil", help="where the files are decoded")
     parser.add_argument("--batch", type=int, default=128)
+    parser.add_argument("--fid", action="store_true", help="also the Inception-v3 FID column")
+    parser.add_argument("--inception_weights", type=str, default=None,
+                        help="pt_inception-2015-12-05-6726825d.pth (default: HAIRFAST_INCEPTION_WEIGHTS or torch's hub cache)")
     args = parser.parse_args(argv)
 
     def load(path):
@@ -240,17 +248,27 @@ def main(argv=None, feature=None, lib=None, device=None):
     datasets = {source: load(args.source_dataset)}
     for method, path in args.methods_dataset:
         datasets[method] = load(path)
-    fids = compute_fid_datasets(datasets, source, feature if feature is not None else ClipModel(lib=lib), args.batch, lib)
-    rows = [(name, str(round(value, 2))) for name, value in fids.items()]  # DataFrame.round(2).to_csv's digits
-    print(f"{'':<24}{'FID_CLIP':>10}")
-    for name, value in rows:
-        print(f"{name:<24}{value:>10}")
+    columns = {}
+    if args.fid:
+        if inception is None:
+            from .checkpoints import inception_fid
+            from .inception import InceptionV3
+
+            inception = InceptionV3(2048, weights=inception_fid(path=args.inception_weights), lib=lib)
+            inception = inception.to(device if device is not None else "cuda")
+        columns["FID"] = compute_fid_datasets(datasets, source, inception, args.batch, lib)
+    columns["FID_CLIP"] = compute_fid_datasets(datasets, source, feature if feature is not None else ClipModel(lib=lib), args.batch, lib)
+    names = list(columns["FID_CLIP"])
+    rows = [(name, *(str(round(col[name], 2)) for col in columns.values())) for name in names]  # DataFrame.round(2).to_csv's digits
+    print(f"{'':<24}" + "".join(f"{c:>10}" for c in columns))
+    for name, *values in rows:
+        print(f"{name:<24}" + "".join(f"{v:>10}" for v in values))
     os.makedirs(args.output.parent, exist_ok=True)
     with open(args.output, "w", newline="") as f:
         out = csv.writer(f)
-        out.writerow(["", "FID_CLIP"])
+        out.writerow(["", *columns])
         out.writerows(rows)
-    return fids
+    return columns if args.fid else columns["FID_CLIP"]
 
 
 if __name__ == "__main__":

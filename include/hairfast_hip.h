@@ -915,6 +915,40 @@ int hf_l2_normalize_rows_f32(float *out, float *norms, const float *x, int rows,
 int hf_row_similarity_f64(double *out, const float *a, const float *b, int n, int m, int d, int paired, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * FID Inception-v3 (csrc/conv_rect.h, csrc/inception.h; torch-fidelity's FeatureExtractorInceptionV3, the network of
+ * torchmetrics' FrechetInceptionDistance in scripts/fid_metric.py).  One owner per output element, every sum in a fixed
+ * order that does not depend on the batch: an image's bits depend neither on the batch size nor on its position in it.
+ *
+ * hf_conv2d_rect_f16_f32: a convolution over a kh x kw rectangle of taps between channel slices of NCHW tensors,
+ *   y[n, oc0+co, oy, ox] = act(out_scale[co] * sum_{ky,kx,ci} W[co,ci,ky,kx] * x[n, xc0+ci, oy*stride-pad_top+ky, ox*stride-pad_left+kx]
+ *                              + bias[co])
+ * with zero outside the plane.  x [batch, x_ctotal, h, w] is read at channels xc0 .. xc0+cin-1, out [batch, o_ctotal, out_h,
+ * out_w] written at channels oc0 .. oc0+cout-1 and nowhere else.  out_scale / bias [cout] may be NULL (1 / 0); act 0 = none,
+ * 1 = ReLU.  kh, kw in 1..7, stride 1 or 2, 0 <= pad_top < kh, 0 <= pad_left < kw, any cin, cout >= 1; the caller states
+ * out_h, out_w (the last output's first tap must not lie beyond the plane).
+ * nterms 3 / 1: the fp16 matrix cores in the operand modes of hf_conv1x1_f16_f32; wt_hi / wt_lo are
+ *   hf_conv_split_weights_f16_taps(taps = 1, kh*kw*cinp, coutp) of the fp32 table [tap*cinp + ci][co] = W[co,ci,ky,kx], tap =
+ *   ky*kw + kx, cinp = cin rounded up to 32, coutp = cout rounded up to 64, the padding zero (wt_lo may be NULL for nterms 1);
+ *   products are summed in (tap, ci) order, K is never split.
+ * nterms 0: exact fp32 FMA in ascending (ky, kx, ci), one lane per output; weight = W [cout][cin][kh][kw] (torch's layout).
+ * Anything else returns HF_E_INVALID. */
+int hf_conv2d_rect_f16_f32(float *out, const float *x, const float *weight, const void *wt_hi, const void *wt_lo, int nterms,
+                           const float *out_scale, const float *bias, int act, int batch, int cin, int cout, int h, int w, int kh,
+                           int kw, int stride, int pad_top, int pad_left, int out_h, int out_w, int xc0, int x_ctotal, int oc0,
+                           int o_ctotal, void *stream);
+/* 3x3 pooling between channel slices (addressing as above; c channels): mode 0 = maximum (padding ignored), 1 = average
+ * that does not count padding (the real pixels are added in row-major order in fp32 and divided by their number).
+ * stride 1: pad 1, the plane keeps its size; stride 2: pad 0, floor mode, h, w >= 3.  Other strides: HF_E_INVALID. */
+int hf_pool3x3_f32(float *out, const float *x, int mode, int n, int c, int h, int w, int stride, int xc0, int x_ctotal, int oc0,
+                   int o_ctotal, void *stream);
+/* TF1-style bilinear resize (align_corners = False, NO half-pixel offset): x [n,c,h,w] uint8 (is_u8 != 0) or fp32 ->
+ * out [n,c,oh,ow] fp32.  Per axis scale = in / out, src = o * scale, i0 = floor(src), i1 = min(i0 + 1, in - 1), t = src - i0;
+ * the horizontal lerp a + (b - a) * tx first, then the vertical one, every operation rounded to fp32 on its own; affine != 0:
+ * out = v * mul + add (two roundings; exact up to the last one when mul is a power of two).  Sizes up to 2^23. */
+int hf_resize_bilinear_tf1_f32(float *out, const void *x, int is_u8, int n, int c, int h, int w, int oh, int ow, int affine,
+                               float mul, float add, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Tuning / debugging hook (no reference counterpart): force the tile
  * configuration hf_modconv3x3_f32 / hf_modconv3x3_up_f32 dispatch to
  * (see the switch statements at the bottom of csrc/modconv.hip); 0 restores the
