@@ -27,11 +27,13 @@
 // (one 24-byte copy per sweep) to stop: converged when no pair is above the threshold - the next sweep would be the
 // identity - or when off <= eps |A|_F.  The absolute test alone cannot be met in general: the skip rule may leave d^2
 // elements of the size of its threshold behind.
+// metric_common.h: hf_block_sum_f64 (jacobi_norms, frechet_finish: three sums through one red, a barrier between them),
+// hf_aligned.
 #pragma once
 #include <cmath>
 #include <cstdint>
 
-#include "hf_common.h"
+#include "metric_common.h"
 
 namespace {
 
@@ -215,19 +217,6 @@ __global__ __launch_bounds__(256) void jacobi_round(double *__restrict__ a_out, 
   }
 }
 
-// sum over the 256 threads of a block through LDS (a tree of a fixed shape); every thread must call it, thread 0 gets the sum
-__device__ __forceinline__ double frechet_block_sum(double v, double *red) {
-  const int tid = threadIdx.x;
-  __syncthreads();  // red may still be read from the previous sum
-  red[tid] = v;
-  __syncthreads();
-  for (int h = 128; h >= 1; h >>= 1) {
-    if (tid < h) red[tid] += red[tid + h];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 // one block: scal[0] = off-diagonal Frobenius norm, scal[1] = Frobenius norm, scal[2] = pairs above the skip threshold
 __global__ __launch_bounds__(256) void jacobi_norms(double *__restrict__ scal, const double *__restrict__ a, int d) {
   HF_DYN_LDS;
@@ -245,9 +234,12 @@ __global__ __launch_bounds__(256) void jacobi_norms(double *__restrict__ scal, c
       if (fabs(v) > kFrEps * sqrt(fabs(a[(long long)r * d + r] * a[(long long)c * d + c]))) above += 1.0;
     }
   }
-  off = frechet_block_sum(off, red);
-  diag = frechet_block_sum(diag, red);
-  above = frechet_block_sum(above, red);
+  __syncthreads();  // as before every sum: red[0] of the one before may still be read
+  off = hf_block_sum_f64(off, red);
+  __syncthreads();
+  diag = hf_block_sum_f64(diag, red);
+  __syncthreads();
+  above = hf_block_sum_f64(above, red);
   if (threadIdx.x == 0) {
     scal[0] = sqrt(2.0 * off);
     scal[1] = sqrt(2.0 * off + diag);
@@ -341,9 +333,12 @@ __global__ __launch_bounds__(256) void frechet_finish(double *__restrict__ out, 
     trace += s1[(long long)i * d + i] + s2[(long long)i * d + i];
     roots += sqrt(fmax(ev[i], 0.0));
   }
-  dist = frechet_block_sum(dist, red);
-  trace = frechet_block_sum(trace, red);
-  roots = frechet_block_sum(roots, red);
+  __syncthreads();  // as before every sum: red[0] of the one before may still be read
+  dist = hf_block_sum_f64(dist, red);
+  __syncthreads();
+  trace = hf_block_sum_f64(trace, red);
+  __syncthreads();
+  roots = hf_block_sum_f64(roots, red);
   if (threadIdx.x == 0) out[0] = dist + trace - 2.0 * roots;
 }
 
@@ -351,8 +346,6 @@ inline int frechet_grid(long long n) {
   const long long g = (n + 255) / 256;
   return (int)(g > 4096 ? 4096 : (g < 1 ? 1 : g));
 }
-
-inline bool frechet_aligned(const void *p, unsigned a) { return p && ((uintptr_t)p & (a - 1)) == 0; }
 
 // the three doubles of jacobi_norms on the host: the one synchronisation of a sweep
 inline int jacobi_read_norms(double *host, const double *dev, hipStream_t st) {
@@ -368,7 +361,7 @@ inline int jacobi_read_norms(double *host, const double *dev, hipStream_t st) {
 
 template <typename T>
 int frechet_accumulate_launch(double *sum, double *cov_sum, const T *feats, int n, int d, void *stream) {
-  if (!frechet_aligned(sum, 8) || !frechet_aligned(cov_sum, 8) || !frechet_aligned(feats, sizeof(T)) || n <= 0 || d <= 0 ||
+  if (!hf_aligned(sum, 8) || !hf_aligned(cov_sum, 8) || !hf_aligned(feats, sizeof(T)) || n <= 0 || d <= 0 ||
       d > 65535 * kFrTile)
     return HF_E_INVALID;
   const int tiles = hf_cdiv(d, kFrTile);
@@ -388,7 +381,7 @@ extern "C" int hf_frechet_accumulate_f16_f64(double *sum, double *cov_sum, const
 }
 
 extern "C" int hf_frechet_stats_f64(double *mu, double *cov, const double *sum, const double *cov_sum, long long n, int d, void *stream) {
-  if (!frechet_aligned(mu, 8) || !frechet_aligned(cov, 8) || !frechet_aligned(sum, 8) || !frechet_aligned(cov_sum, 8) || n < 2 || d <= 0)
+  if (!hf_aligned(mu, 8) || !hf_aligned(cov, 8) || !hf_aligned(sum, 8) || !hf_aligned(cov_sum, 8) || n < 2 || d <= 0)
     return HF_E_INVALID;
   hipLaunchKernelGGL(frechet_stats, dim3(frechet_grid((long long)d * d)), dim3(256), 0, (hipStream_t)stream, mu, cov, sum, cov_sum,
                      (double)n, d);
@@ -401,7 +394,7 @@ extern "C" long long hf_sym_eig_jacobi_work_doubles(int d, int want_vectors) {
 
 extern "C" int hf_sym_eig_jacobi_f64(double *w, double *v, const double *a, double *work, int d, int max_sweeps, int *sweeps,
                                      double *off_norm, void *stream) {
-  if (!frechet_aligned(w, 8) || (v && !frechet_aligned(v, 8)) || !frechet_aligned(a, 8) || !frechet_aligned(work, 8) || d <= 0 ||
+  if (!hf_aligned(w, 8) || (v && !hf_aligned(v, 8)) || !hf_aligned(a, 8) || !hf_aligned(work, 8) || d <= 0 ||
       d > 16384 || max_sweeps < 1 || !sweeps || !off_norm)
     return HF_E_INVALID;
   const hipStream_t st = (hipStream_t)stream;
@@ -436,8 +429,8 @@ extern "C" int hf_sym_eig_jacobi_f64(double *w, double *v, const double *a, doub
 
 extern "C" int hf_frechet_congruence_f64(double *m_out, const double *w, const double *v, const double *s2, double *work, int d,
                                          void *stream) {
-  if (!frechet_aligned(m_out, 8) || !frechet_aligned(w, 8) || !frechet_aligned(v, 8) || !frechet_aligned(s2, 8) ||
-      !frechet_aligned(work, 8) || d <= 0 || d > 65535 * kFrGemm)
+  if (!hf_aligned(m_out, 8) || !hf_aligned(w, 8) || !hf_aligned(v, 8) || !hf_aligned(s2, 8) ||
+      !hf_aligned(work, 8) || d <= 0 || d > 65535 * kFrGemm)
     return HF_E_INVALID;
   const hipStream_t st = (hipStream_t)stream;
   double *t = work, *u = work + (long long)d * d;
@@ -451,8 +444,8 @@ extern "C" int hf_frechet_congruence_f64(double *m_out, const double *w, const d
 
 extern "C" int hf_frechet_finish_f64(double *out, const double *mu1, const double *mu2, const double *s1, const double *s2,
                                      const double *ev, int d, void *stream) {
-  if (!frechet_aligned(out, 8) || !frechet_aligned(mu1, 8) || !frechet_aligned(mu2, 8) || !frechet_aligned(s1, 8) ||
-      !frechet_aligned(s2, 8) || !frechet_aligned(ev, 8) || d <= 0)
+  if (!hf_aligned(out, 8) || !hf_aligned(mu1, 8) || !hf_aligned(mu2, 8) || !hf_aligned(s1, 8) ||
+      !hf_aligned(s2, 8) || !hf_aligned(ev, 8) || d <= 0)
     return HF_E_INVALID;
   hipLaunchKernelGGL(frechet_finish, dim3(1), dim3(256), 256 * sizeof(double), (hipStream_t)stream, out, mu1, mu2, s1, s2, ev, d);
   return hf_launch_status();

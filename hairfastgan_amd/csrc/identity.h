@@ -7,11 +7,12 @@
 //
 // Plain vector stores, no atomics; every output element has ONE owner and every sum a fixed order: an image's, a row's or an
 // entry's bits depend on its own data alone, never on how many others the launch holds.
+// metric_common.h: hf_block_sum_f64 (l2_normalize_rows), hf_aligned, hf_lane_blocks (hf_crop_avgpool_f32).
 #pragma once
 #include <cmath>
 #include <cstdint>
 
-#include "hf_common.h"
+#include "metric_common.h"
 
 namespace {
 
@@ -58,13 +59,7 @@ __global__ __launch_bounds__(256) void l2_normalize_rows(float *__restrict__ out
     const double v = (double)xr[k];
     s += v * v;
   }
-  red[tid] = s;
-  __syncthreads();
-  for (int hlf = 128; hlf >= 1; hlf >>= 1) {
-    if (tid < hlf) red[tid] += red[tid + hlf];
-    __syncthreads();
-  }
-  const float norm = (float)sqrt(red[0]);
+  const float norm = (float)sqrt(hf_block_sum_f64(s, red));
   for (int k = tid; k < d; k += 256) out[(long long)blockIdx.x * d + k] = xr[k] / norm;
   if (norms && tid == 0) norms[blockIdx.x] = norm;
 }
@@ -93,30 +88,29 @@ __global__ __launch_bounds__(256) void row_similarity(double *__restrict__ out, 
   if (lane == 0 && e < entries) out[e] = red[tid];
 }
 
-inline bool id_aligned(const void *p, unsigned al) { return p && ((uintptr_t)p & (al - 1)) == 0; }
-
 }  // namespace
 
 extern "C" int hf_crop_avgpool_f32(float *out, const float *x, const float *scale, const float *shift, int n, int c, int h, int w,
                                    int y0, int x0, int ch, int cw, int oh, int ow, void *stream) {
-  if (!id_aligned(out, 4) || !id_aligned(x, 4) || n <= 0 || c <= 0 || h <= 0 || w <= 0 || ch <= 0 || cw <= 0 || oh <= 0 || ow <= 0 ||
+  if (!hf_aligned(out, 4) || !hf_aligned(x, 4) || n <= 0 || c <= 0 || h <= 0 || w <= 0 || ch <= 0 || cw <= 0 || oh <= 0 || ow <= 0 ||
       y0 < 0 || x0 < 0 || (long long)y0 + ch > h || (long long)x0 + cw > w || (long long)h * w > 0x7fffffffLL)
     return HF_E_INVALID;
-  const long long total = (long long)n * c * oh * ow, blocks = (total + 255) / 256;
-  if (blocks > 0x7fffffffLL) return HF_E_INVALID;
-  hipLaunchKernelGGL(crop_avgpool, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out, x, scale, shift, c, h, w, y0, x0, ch,
+  const long long total = (long long)n * c * oh * ow;
+  unsigned blocks;
+  if (!hf_lane_blocks(total, blocks)) return HF_E_INVALID;
+  hipLaunchKernelGGL(crop_avgpool, dim3(blocks), dim3(256), 0, (hipStream_t)stream, out, x, scale, shift, c, h, w, y0, x0, ch,
                      cw, oh, ow, total);
   return hf_launch_status();
 }
 
 extern "C" int hf_l2_normalize_rows_f32(float *out, float *norms, const float *x, int rows, int d, void *stream) {
-  if (!id_aligned(out, 4) || !id_aligned(x, 4) || (norms && !id_aligned(norms, 4)) || rows <= 0 || d <= 0) return HF_E_INVALID;
+  if (!hf_aligned(out, 4) || !hf_aligned(x, 4) || (norms && !hf_aligned(norms, 4)) || rows <= 0 || d <= 0) return HF_E_INVALID;
   hipLaunchKernelGGL(l2_normalize_rows, dim3(rows), dim3(256), 256 * sizeof(double), (hipStream_t)stream, out, norms, x, d);
   return hf_launch_status();
 }
 
 extern "C" int hf_row_similarity_f64(double *out, const float *a, const float *b, int n, int m, int d, int paired, void *stream) {
-  if (!id_aligned(out, 8) || !id_aligned(a, 4) || !id_aligned(b, 4) || n <= 0 || m <= 0 || d <= 0 || (paired && n != m))
+  if (!hf_aligned(out, 8) || !hf_aligned(a, 4) || !hf_aligned(b, 4) || n <= 0 || m <= 0 || d <= 0 || (paired && n != m))
     return HF_E_INVALID;
   const long long entries = paired ? n : (long long)n * m, blocks = (entries + kSimWaves - 1) / kSimWaves;
   if (blocks > 0x7fffffffLL) return HF_E_INVALID;

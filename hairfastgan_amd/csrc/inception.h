@@ -8,11 +8,12 @@
 //                                images to fp32, with an optional affine of the result
 //
 // Plain vector stores, no atomics; every output element has ONE owner and every sum a fixed order.
+// metric_common.h: hf_aligned, hf_lane_blocks (both launchers).
 #pragma once
 #include <cmath>
 #include <cstdint>
 
-#include "hf_common.h"
+#include "metric_common.h"
 
 namespace {
 
@@ -80,31 +81,33 @@ __global__ __launch_bounds__(256) void resize_bilinear_tf1(float *__restrict__ o
 
 extern "C" int hf_pool3x3_f32(float *out, const float *x, int mode, int n, int c, int h, int w, int stride, int xc0, int x_ctotal,
                               int oc0, int o_ctotal, void *stream) {
-  if (!out || !x || ((uintptr_t)out & 3) || ((uintptr_t)x & 3) || (mode != 0 && mode != 1) || n <= 0 || c <= 0 || h <= 0 || w <= 0 ||
+  if (!hf_aligned(out, 4) || !hf_aligned(x, 4) || (mode != 0 && mode != 1) || n <= 0 || c <= 0 || h <= 0 || w <= 0 ||
       (stride != 1 && stride != 2) || (stride == 2 && (h < 3 || w < 3)) || xc0 < 0 || oc0 < 0 || (long long)xc0 + c > x_ctotal ||
       (long long)oc0 + c > o_ctotal || (long long)h * w > 0x7fffffffLL)
     return HF_E_INVALID;
   const int pad = stride == 1 ? 1 : 0;
   const int oh = stride == 1 ? h : (h - 3) / 2 + 1, ow = stride == 1 ? w : (w - 3) / 2 + 1;
-  const long long total = (long long)n * c * oh * ow, blocks = (total + 255) / 256;
-  if (blocks > 0x7fffffffLL) return HF_E_INVALID;
-  hipLaunchKernelGGL(pool3x3, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out, x, mode, c, h, w, stride, pad, oh, ow,
+  const long long total = (long long)n * c * oh * ow;
+  unsigned blocks;
+  if (!hf_lane_blocks(total, blocks)) return HF_E_INVALID;
+  hipLaunchKernelGGL(pool3x3, dim3(blocks), dim3(256), 0, (hipStream_t)stream, out, x, mode, c, h, w, stride, pad, oh, ow,
                      xc0, x_ctotal, oc0, o_ctotal, total);
   return hf_launch_status();
 }
 
 extern "C" int hf_resize_bilinear_tf1_f32(float *out, const void *x, int is_u8, int n, int c, int h, int w, int oh, int ow, int affine,
                                           float mul, float add, void *stream) {
-  if (!out || !x || ((uintptr_t)out & 3) || (!is_u8 && ((uintptr_t)x & 3)) || n <= 0 || c <= 0 || h <= 0 || w <= 0 || oh <= 0 ||
+  if (!hf_aligned(out, 4) || !hf_aligned(x, is_u8 ? 1 : 4) || n <= 0 || c <= 0 || h <= 0 || w <= 0 || oh <= 0 ||
       ow <= 0 || h > (1 << 23) || w > (1 << 23) || oh > (1 << 23) || ow > (1 << 23) || (long long)h * w > 0x7fffffffLL)
     return HF_E_INVALID;
-  const long long total = (long long)n * c * oh * ow, blocks = (total + 255) / 256;
-  if (blocks > 0x7fffffffLL) return HF_E_INVALID;
+  const long long total = (long long)n * c * oh * ow;
+  unsigned blocks;
+  if (!hf_lane_blocks(total, blocks)) return HF_E_INVALID;
   if (is_u8)
-    hipLaunchKernelGGL(resize_bilinear_tf1<unsigned char>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out,
+    hipLaunchKernelGGL(resize_bilinear_tf1<unsigned char>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, out,
                        static_cast<const unsigned char *>(x), h, w, oh, ow, affine ? 1 : 0, mul, add, total);
   else
-    hipLaunchKernelGGL(resize_bilinear_tf1<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out,
+    hipLaunchKernelGGL(resize_bilinear_tf1<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, out,
                        static_cast<const float *>(x), h, w, oh, ow, affine ? 1 : 0, mul, add, total);
   return hf_launch_status();
 }

@@ -10,11 +10,12 @@
 // Plain vector stores, no floating-point atomics; every output element has ONE owner and every sum a fixed order: results do
 // not depend on timing, and a sample's bits depend neither on the batch size nor on its place in the batch (the grid's
 // partition of a sample follows from the sample's shape alone).
+// metric_common.h: hf_block_sum_f64 (sq_err_partial, metric_finish), hf_aligned.
 #pragma once
 #include <cmath>
 #include <cstdint>
 
-#include "hf_common.h"
+#include "metric_common.h"
 
 namespace {
 
@@ -168,13 +169,8 @@ __global__ __launch_bounds__(256) void sq_err_partial(double *__restrict__ part,
     const double d = (double)pa[e] - (double)pb[e];
     s += d * d;
   }
-  red[tid] = s;
-  __syncthreads();
-  for (int h = 128; h >= 1; h >>= 1) {
-    if (tid < h) red[tid] += red[tid + h];
-    __syncthreads();
-  }
-  if (tid == 0) part[(long long)n * gridDim.x + blockIdx.x] = red[0];
+  const double total = hf_block_sum_f64(s, red);
+  if (tid == 0) part[(long long)n * gridDim.x + blockIdx.x] = total;
 }
 
 // grid (n), 256 threads, LDS [256] fp64: thread t adds part[n][t], part[n][t + 256], ... in that order, a tree of fixed shape
@@ -187,19 +183,12 @@ __global__ __launch_bounds__(256) void metric_finish(double *__restrict__ out, c
   const int tid = threadIdx.x, n = blockIdx.x;
   double s = 0.0;
   for (int e = tid; e < blocks; e += 256) s += part[(long long)n * blocks + e];
-  red[tid] = s;
-  __syncthreads();
-  for (int h = 128; h >= 1; h >>= 1) {
-    if (tid < h) red[tid] += red[tid + h];
-    __syncthreads();
-  }
+  const double total = hf_block_sum_f64(s, red);
   if (tid == 0) {
-    const double v = red[0] * scale;
+    const double v = total * scale;
     out[n] = accumulate ? out[n] + v : v;
   }
 }
-
-inline bool lpips_aligned(const void *p, unsigned a) { return p && ((uintptr_t)p & (a - 1)) == 0; }
 
 inline int sq_err_blocks(long long per_image) {
   const long long b = (per_image + 256LL * kSqPerThread - 1) / (256LL * kSqPerThread);
@@ -211,7 +200,7 @@ inline int sq_err_blocks(long long per_image) {
 extern "C" int hf_conv2d_direct_f32(float *out, const float *x, const float *weight, const float *in_scale, const float *in_shift,
                                     const float *bias, int act, float alpha, int n, int cin, int cout, int h, int w, int k, int stride,
                                     int pad, void *stream) {
-  if (!lpips_aligned(out, 4) || !lpips_aligned(x, 4) || !lpips_aligned(weight, 4) || n <= 0 || n > 65535 || cin <= 0 ||
+  if (!hf_aligned(out, 4) || !hf_aligned(x, 4) || !hf_aligned(weight, 4) || n <= 0 || n > 65535 || cin <= 0 ||
       cin > kDcMaxCin || cout <= 0 || cout > 65535 * kDcCout || k <= 0 || k > kDcMaxK || stride < 1 || stride > 4 || pad < 0 ||
       pad >= k || h <= 0 || w <= 0 || h + 2 * pad < k || w + 2 * pad < k || (act != kActNone && act != kActLrelu))
     return HF_E_INVALID;
@@ -224,7 +213,7 @@ extern "C" int hf_conv2d_direct_f32(float *out, const float *x, const float *wei
 }
 
 extern "C" int hf_maxpool2d_f32(float *out, const float *x, long long planes, int h, int w, int k, int stride, void *stream) {
-  if (!lpips_aligned(out, 4) || !lpips_aligned(x, 4) || planes <= 0 || (k != 2 && k != 3) || stride < 1 || stride > k || h < k ||
+  if (!hf_aligned(out, 4) || !hf_aligned(x, 4) || planes <= 0 || (k != 2 && k != 3) || stride < 1 || stride > k || h < k ||
       w < k)
     return HF_E_INVALID;
   const int oh = (h - k) / stride + 1, ow = (w - k) / stride + 1;
@@ -240,7 +229,7 @@ extern "C" long long hf_lpips_layer_work_doubles(int n, int h, int w) {
 
 extern "C" int hf_lpips_layer_f64(double *dist, const float *fx, const float *fy, const float *lin_w, double *work, int n, int c,
                                   int h, int w, int accumulate, void *stream) {
-  if (!lpips_aligned(dist, 8) || !lpips_aligned(fx, 4) || !lpips_aligned(fy, 4) || !lpips_aligned(lin_w, 4) || !lpips_aligned(work, 8) ||
+  if (!hf_aligned(dist, 8) || !hf_aligned(fx, 4) || !hf_aligned(fy, 4) || !hf_aligned(lin_w, 4) || !hf_aligned(work, 8) ||
       n <= 0 || n > 65535 || c <= 0 || h <= 0 || w <= 0 || (long long)h * w > 0x7fffffffLL - kLpPixels)
     return HF_E_INVALID;
   const int hw = h * w, blocks = hf_cdiv(hw, kLpPixels);
@@ -259,7 +248,7 @@ extern "C" long long hf_sq_err_sum_work_doubles(int n, long long per_image) {
 extern "C" int hf_sq_err_sum_f64(double *out, const void *a, const void *b, double *work, int n, long long per_image, int is_u8,
                                  void *stream) {
   const unsigned align = is_u8 ? 1 : 4;
-  if (!lpips_aligned(out, 8) || !lpips_aligned(a, align) || !lpips_aligned(b, align) || !lpips_aligned(work, 8) || n <= 0 || n > 65535 ||
+  if (!hf_aligned(out, 8) || !hf_aligned(a, align) || !hf_aligned(b, align) || !hf_aligned(work, 8) || n <= 0 || n > 65535 ||
       per_image <= 0)
     return HF_E_INVALID;
   const int blocks = sq_err_blocks(per_image);

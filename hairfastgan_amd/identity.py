@@ -17,8 +17,6 @@ Inference only: Dropout is the identity and the BatchNorms use their running sta
 sources; the network's layers go through `encoders._fused`, which asks `_fused.lib()`.
 """
 import argparse
-import json
-import os
 
 import torch
 from torch import nn
@@ -26,7 +24,7 @@ from torch import nn
 from . import _marshal as M
 from .encoders import _fused as FU
 from .encoders.e4e import _IR_UNITS, bottleneck_IR_SE
-from .metrics import _backend, list_image_files
+from .metrics import _backend, add_pair_arguments, score_pairs, unit_range
 
 CROP = (35, 32, 188, 188)  # (y0, x0, height, width): x[:, :, 35:223, 32:220], the face of a 256^2 aligned image
 
@@ -179,47 +177,25 @@ class IDLoss(nn.Module):
 
 def main(argv=None, model=None, lib=None, device=None):
     """Scores every file of --data_path against the file of the same name in --gt_path and writes
-    inference_metrics/scores_id.json (file -> similarity) and stat_id.txt next to --data_path.  `model`: an IDLoss (default:
-    the IR-SE50 with the weights of --weights or of `checkpoints.arcface`).  -> {file name: similarity}."""
-    from .lpips import load_pairs
-
+    inference_metrics/scores_id.json (file -> similarity) and stat_id.txt next to --data_path (`metrics.score_pairs`).
+    `model`: an IDLoss (default: the IR-SE50 with the weights of --weights or of `checkpoints.arcface`).
+    -> {file name: similarity}."""
     parser = argparse.ArgumentParser(prog="python -m hairfastgan_amd.identity", description="identity similarity of a folder of results")
-    parser.add_argument("--data_path", type=str, default="results")
-    parser.add_argument("--gt_path", type=str, default="gt_images")
-    parser.add_argument("--size", type=int, default=256)
-    parser.add_argument("--image_decoder", choices=("pil", "device"), default="pil", help="where the files are decoded")
-    parser.add_argument("--batch", type=int, default=8)
+    add_pair_arguments(parser, batch=8)
     parser.add_argument("--weights", type=str, default=None, help="ir_se50.pth (default: pretrained_models/ArcFace/ir_se50.pth)")
     args = parser.parse_args(argv)
-    names = list_image_files(args.data_path)
-    missing = [f for f in names if not os.path.isfile(os.path.join(args.gt_path, f))]
-    if missing:
-        raise FileNotFoundError(f"no ground truth for {missing[0]} in '{args.gt_path}'")
-    if model is None:
-        from .checkpoints import ARCFACE_PATH, arcface
 
-        facenet = Backbone(input_size=112, num_layers=50, drop_ratio=0.6, mode="ir_se")
-        facenet.load_state_dict(arcface(path=args.weights or ARCFACE_PATH))
-        model = IDLoss(facenet.to(device if device is not None else "cuda"), lib=lib)
-    scores = {}
-    for k in range(0, len(names), max(args.batch, 1)):
-        part = names[k:k + max(args.batch, 1)]
-        res, gt = load_pairs(args.data_path, args.gt_path, part, args.size, args.image_decoder, device, lib)
-        # ToTensor + Normalize(0.5, 0.5): [-1, 1]
-        values = model.similarity((res.float() / 255 - 0.5) / 0.5, (gt.float() / 255 - 0.5) / 0.5)
-        scores.update(zip(part, values.tolist()))  # one copy per batch
-    values = torch.tensor(list(scores.values()), dtype=torch.float64)
-    mean = float(values.mean()) if len(scores) else float("nan")
-    std = float(values.std(unbiased=False)) if len(scores) else float("nan")
-    result_str = "Average similarity is {:.2f}+-{:.2f}".format(mean, std)
-    print(result_str)
-    out_path = os.path.join(os.path.dirname(args.data_path), "inference_metrics")
-    os.makedirs(out_path, exist_ok=True)
-    with open(os.path.join(out_path, "stat_id.txt"), "w") as f:
-        f.write(result_str)
-    with open(os.path.join(out_path, "scores_id.json"), "w") as f:
-        json.dump(scores, f)
-    return scores
+    def score(res, gt):
+        nonlocal model
+        if model is None:
+            from .checkpoints import ARCFACE_PATH, arcface
+
+            facenet = Backbone(input_size=112, num_layers=50, drop_ratio=0.6, mode="ir_se")
+            facenet.load_state_dict(arcface(path=args.weights or ARCFACE_PATH))
+            model = IDLoss(facenet.to(device if device is not None else "cuda"), lib=lib)
+        return model.similarity(unit_range(res), unit_range(gt))
+
+    return score_pairs(args, score, "id", "Average similarity is {:.2f}+-{:.2f}", device, lib)
 
 
 if __name__ == "__main__":

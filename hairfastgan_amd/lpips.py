@@ -17,15 +17,14 @@ The SqueezeNet tower, the masked and the scale-weighted variants and everything 
 sources; the tower's 3x3 layers go through `encoders._fused`, which asks `_fused.lib()`.
 """
 import argparse
-import json
-import os
 
 import torch
 from torch import nn
 
 from . import _marshal as M
 from .encoders import _fused as FU
-from .metrics import _backend, list_image_files
+from .metrics import _backend, add_pair_arguments, score_pairs, unit_range
+from .metrics import load_pairs  # noqa: F401  re-exported: callers name hairfastgan_amd.lpips.load_pairs
 
 ALEX_CONVS = ((0, 3, 64, 11, 4, 2), (3, 64, 192, 5, 1, 2), (6, 192, 384, 3, 1, 1), (8, 384, 256, 3, 1, 1),
               (10, 256, 256, 3, 1, 1))  # torchvision alexnet.features: (index, cin, cout, k, stride, pad)
@@ -161,66 +160,32 @@ def psnr(x, y, data_range=None, lib=None):
     return 10.0 * torch.log10(float(data_range) ** 2 / mse(x, y, lib))
 
 
-def load_pairs(data_path, gt_path, names, size, decoder="pil", device=None, lib=None):
-    """-> (results, ground truth) uint8 [N,3,size,size]: the files `names` of both folders, each byte-equal to
-    `Image.open(p).convert("RGB").resize((size, size), BILINEAR)`."""
-    from . import face_align as FA
-    from .image_utils import read_images
-
-    device = torch.device(device if device is not None else "cuda")
-    out = []
-    for folder in (data_path, gt_path):
-        images = [t.to(device).contiguous() for t in read_images([os.path.join(folder, f) for f in names], decoder=decoder)]
-        L, st = _backend(lib, *images)
-        out.append(torch.stack([FA.resize_bilinear(L, st, img, size, size) for img in images]))
-    return out
-
-
 def main(argv=None, model=None, lib=None, device=None):
     """The command line of calc_losses_on_images.py: scores every file of --data_path against the file of the same name in
-    --gt_path and writes inference_metrics/scores_<mode>.json and stat_<mode>.txt next to --data_path.  `model`: the LPIPS
-    module (default: LPIPS(--net) with the weights `checkpoints.lpips_weights` finds).  -> {file name: score}."""
+    --gt_path and writes inference_metrics/scores_<mode>.json and stat_<mode>.txt next to --data_path (`metrics.score_pairs`).
+    `model`: the LPIPS module (default: LPIPS(--net) with the weights `checkpoints.lpips_weights` finds).
+    -> {file name: score}."""
     parser = argparse.ArgumentParser(prog="python -m hairfastgan_amd.lpips", description="LPIPS / L2 / PSNR of a folder of results")
     parser.add_argument("--mode", choices=("lpips", "l2", "psnr"), default="lpips")
-    parser.add_argument("--data_path", type=str, default="results")
-    parser.add_argument("--gt_path", type=str, default="gt_images")
     parser.add_argument("--net", choices=("alex", "vgg"), default="alex")
-    parser.add_argument("--size", type=int, default=256)
-    parser.add_argument("--image_decoder", choices=("pil", "device"), default="pil", help="where the files are decoded")
-    parser.add_argument("--batch", type=int, default=4)
+    add_pair_arguments(parser, batch=4)
     args = parser.parse_args(argv)
-    names = list_image_files(args.data_path)
-    missing = [f for f in names if not os.path.isfile(os.path.join(args.gt_path, f))]
-    if missing:
-        raise FileNotFoundError(f"no ground truth for {missing[0]} in '{args.gt_path}'")
-    if args.mode == "lpips" and model is None:
-        from .checkpoints import lpips_weights
 
-        model = LPIPS(args.net, lib=lib)
-        model.load_pretrained(*lpips_weights(args.net))
-        model = model.to(device if device is not None else "cuda")
-    scores = {}
-    for k in range(0, len(names), max(args.batch, 1)):
-        part = names[k:k + max(args.batch, 1)]
-        res, gt = load_pairs(args.data_path, args.gt_path, part, args.size, args.image_decoder, device, lib)
+    def score(res, gt):
+        nonlocal model
         if args.mode == "psnr":
-            values = psnr(res, gt, lib=lib)
-        else:  # ToTensor + Normalize(0.5, 0.5): [-1, 1]
-            x, y = (res.float() / 255 - 0.5) / 0.5, (gt.float() / 255 - 0.5) / 0.5
-            values = model.per_sample(x, y) if args.mode == "lpips" else mse(x, y, lib)
-        scores.update(zip(part, values.tolist()))  # one copy per batch
-    values = torch.tensor(list(scores.values()), dtype=torch.float64)
-    mean = float(values.mean()) if len(scores) else float("nan")
-    std = float(values.std(unbiased=False)) if len(scores) else float("nan")
-    result_str = "Average loss is {:.2f}+-{:.2f}".format(mean, std)
-    print(result_str)
-    out_path = os.path.join(os.path.dirname(args.data_path), "inference_metrics")
-    os.makedirs(out_path, exist_ok=True)
-    with open(os.path.join(out_path, f"stat_{args.mode}.txt"), "w") as f:
-        f.write(result_str)
-    with open(os.path.join(out_path, f"scores_{args.mode}.json"), "w") as f:
-        json.dump(scores, f)
-    return scores
+            return psnr(res, gt, lib=lib)
+        if args.mode == "l2":
+            return mse(unit_range(res), unit_range(gt), lib)
+        if model is None:
+            from .checkpoints import lpips_weights
+
+            model = LPIPS(args.net, lib=lib)
+            model.load_pretrained(*lpips_weights(args.net))
+            model = model.to(device if device is not None else "cuda")
+        return model.per_sample(unit_range(res), unit_range(gt))
+
+    return score_pairs(args, score, args.mode, "Average loss is {:.2f}+-{:.2f}", device, lib)
 
 
 if __name__ == "__main__":

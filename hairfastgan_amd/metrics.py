@@ -14,11 +14,15 @@ The host lists files and copies one double per method back.  The Inception-v3 ha
 is `FrechetDistance(hairfastgan_amd.inception.InceptionV3(2048, weights=...))`, the command line's --fid; its weights are an
 explicit argument (`checkpoints.inception_fid()` finds the published file), never an implicit download.
 
+The command lines that score a folder of results against a folder of ground truth (`lpips`, `identity`) share their file
+handling here: `load_pairs`, `add_pair_arguments`, `unit_range`, `score_pairs`.
+
 Every entry point takes `lib=None`: the loaded HIP library on torch's current stream.  Tests hand in the CPU interpreter
 build of the same kernel sources and CPU tensors.
 """
 import argparse
 import csv
+import json
 import os
 from pathlib import Path
 
@@ -200,6 +204,64 @@ def load_images_299(directory, files, decoder="pil", device=None, lib=None):
         return torch.empty((0, 3, 299, 299), dtype=torch.uint8, device=device)
     L, st = _backend(lib, *images)
     return torch.stack([FA.resize_lanczos(L, st, img.contiguous(), 299, 299) for img in images])
+
+
+def load_pairs(data_path, gt_path, names, size, decoder="pil", device=None, lib=None):
+    """-> (results, ground truth) uint8 [N,3,size,size]: the files `names` of both folders, each byte-equal to
+    `Image.open(p).convert("RGB").resize((size, size), BILINEAR)`."""
+    from . import face_align as FA
+    from .image_utils import read_images
+
+    device = torch.device(device if device is not None else "cuda")
+    out = []
+    for folder in (data_path, gt_path):
+        images = [t.to(device).contiguous() for t in read_images([os.path.join(folder, f) for f in names], decoder=decoder)]
+        L, st = _backend(lib, *images)
+        out.append(torch.stack([FA.resize_bilinear(L, st, img, size, size) for img in images]))
+    return out
+
+
+def add_pair_arguments(parser, batch):
+    """The arguments every paired-folder command line takes (`lpips`, `identity`); `batch`: the default of --batch."""
+    parser.add_argument("--data_path", type=str, default="results")
+    parser.add_argument("--gt_path", type=str, default="gt_images")
+    parser.add_argument("--size", type=int, default=256)
+    parser.add_argument("--image_decoder", choices=("pil", "device"), default="pil", help="where the files are decoded")
+    parser.add_argument("--batch", type=int, default=batch)
+
+
+def score_pairs(args, score, tag, sentence, device=None, lib=None):
+    """The scoring loop of calc_losses_on_images.py: every image file of args.data_path against the file of the same name in
+    args.gt_path (FileNotFoundError when one has none), args.batch pairs at a time.  score(results, ground truth), both uint8
+    [N,3,size,size], -> [N] float64; it is first called after the folders are checked.  Prints `sentence`.format(mean,
+    population std) and writes it to inference_metrics/stat_<tag>.txt and the scores to scores_<tag>.json next to
+    args.data_path.  -> {file name: score}."""
+    names = list_image_files(args.data_path)
+    missing = [f for f in names if not os.path.isfile(os.path.join(args.gt_path, f))]
+    if missing:
+        raise FileNotFoundError(f"no ground truth for {missing[0]} in '{args.gt_path}'")
+    scores = {}
+    for k in range(0, len(names), max(args.batch, 1)):
+        part = names[k:k + max(args.batch, 1)]
+        res, gt = load_pairs(args.data_path, args.gt_path, part, args.size, args.image_decoder, device, lib)
+        scores.update(zip(part, score(res, gt).tolist()))  # one copy per batch
+    values = torch.tensor(list(scores.values()), dtype=torch.float64)
+    mean = float(values.mean()) if len(scores) else float("nan")
+    std = float(values.std(unbiased=False)) if len(scores) else float("nan")
+    result_str = sentence.format(mean, std)
+    print(result_str)
+    out_path = os.path.join(os.path.dirname(args.data_path), "inference_metrics")
+    os.makedirs(out_path, exist_ok=True)
+    with open(os.path.join(out_path, f"stat_{tag}.txt"), "w") as f:
+        f.write(result_str)
+    with open(os.path.join(out_path, f"scores_{tag}.json"), "w") as f:
+        json.dump(scores, f)
+    return scores
+
+
+def unit_range(images_u8):
+    """ToTensor + Normalize(0.5, 0.5) of uint8 images: fp32 in [-1, 1]."""
+    return (images_u8.float() / 255 - 0.5) / 0.5
 
 
 @torch.inference_mode()

@@ -34,6 +34,7 @@ import torch
 from hairfastgan_amd import _marshal as M
 from hairfastgan_amd import metrics as MT
 from tests import frechet_ref as R
+from tests.metric_common import bits, inject, raises
 
 EPS = R.EPS
 MAX_SWEEPS = 30
@@ -57,21 +58,12 @@ def dist_threshold(family, d):
     return thr
 
 
-def _inject(L, device):
-    """metrics' `lib` argument: the interpreter build on CPU tensors, the product's own library on the GPU."""
-    return L if device.type == "cpu" else None
-
-
 def _dev(a, device):
     return torch.from_numpy(np.array(a)).to(device)  # a copy: the references are read-only
 
 
-def _bits(t):
-    return t.cpu().numpy().view(np.uint64)
-
-
 def _same_bits(t, ref):
-    return np.array_equal(_bits(t), np.ascontiguousarray(ref).view(np.uint64))
+    return np.array_equal(bits(t), np.ascontiguousarray(ref).view(np.uint64))
 
 
 # ---- statistics ---------------------------------------------------------------------------------------------------
@@ -138,7 +130,7 @@ def check_reset(L, st, device):
     """The real side survives reset() under reset_real_features=False only."""
     f = _dev(stat_features(67, 24), device)
     for keep in (False, True):
-        fid = MT.FrechetDistance(lambda x: x, reset_real_features=not keep, lib=_inject(L, device))
+        fid = MT.FrechetDistance(lambda x: x, reset_real_features=not keep, lib=inject(L, device))
         assert fid.to(device) is fid and fid.eval() is fid
         fid.update(f, real=True)  # through the feature callable
         fid.update_features(f[:5], real=False)
@@ -178,7 +170,7 @@ def check_eigh(L, st, device, family, d):
     assert resid <= 64.0 * d * EPS and ortho <= 64.0 * d * EPS, (family, d, resid, ortho)
     w0, none = M.sym_eigh_f64(L, st, _dev(a, device), False, MAX_SWEEPS)  # without vectors: the same rotations
     assert none is None and np.array_equal(w0.cpu().numpy(), w)
-    ws, vs = MT.sym_eigh(_dev(a, device), lib=_inject(L, device))  # the public form: ascending, columns permuted alike
+    ws, vs = MT.sym_eigh(_dev(a, device), lib=inject(L, device))  # the public form: ascending, columns permuted alike
     assert np.array_equal(ws.cpu().numpy(), np.sort(w)) and np.array_equal(vs.cpu().numpy(), v[:, np.argsort(w, kind="stable")])
 
 
@@ -193,7 +185,7 @@ def dist_reference(d, n1, n2, pair):
 
 
 def _distance(L, st, device, fa, fb, chunk=64):
-    fid = MT.FrechetDistance(lambda x: x, lib=_inject(L, device))
+    fid = MT.FrechetDistance(lambda x: x, lib=inject(L, device))
     for side, f in ((True, fa), (False, fb)):
         t = _dev(f, device)
         for k in range(0, t.shape[0], chunk):
@@ -224,7 +216,7 @@ def check_distance(L, st, device, d, n1, n2, family):
     # the functional form on the same statistics
     mu1, s1 = M.frechet_stats(L, st, *fid.state(True)[:2], n1)
     mu2, s2 = M.frechet_stats(L, st, *fid.state(False)[:2], n2)
-    assert float(MT.frechet_distance(mu1, s1, mu2, s2, lib=_inject(L, device))) == ab
+    assert float(MT.frechet_distance(mu1, s1, mu2, s2, lib=inject(L, device))) == ab
 
 
 # ---- front end ----------------------------------------------------------------------------------------------------
@@ -246,7 +238,7 @@ def check_clip_model(L, st, device):
     window mean: windows of at most 3 x 3 values in [0,1], 2^-21 absolute, divided by std >= 0.26) and its output is returned."""
     images = torch.from_numpy(np.random.default_rng(3).integers(0, 256, (2, 3, 299, 299), dtype=np.uint8)).to(device)
     tower = RecordingTower(device)
-    out = MT.ClipModel(tower, lib=_inject(L, device))(images)
+    out = MT.ClipModel(tower, lib=inject(L, device))(images)
     x = torch.nn.functional.adaptive_avg_pool2d(images.cpu().float() / 255, (224, 224))
     mean = torch.tensor(MT.CLIP_MEAN)[None, :, None, None]
     std = torch.tensor(MT.CLIP_STD)[None, :, None, None]
@@ -254,7 +246,7 @@ def check_clip_model(L, st, device):
     assert tower.seen.shape == (2, 3, 224, 224) and tower.seen.dtype == torch.float32
     assert float((tower.seen.cpu() - want).abs().max()) <= 2.0 ** -21 / 0.26
     assert torch.equal(out, RecordingTower(device).encode_image(tower.seen))
-    floats = MT.ClipModel(tower, lib=_inject(L, device))(images.float() / 255)  # [0,1] floats are taken as they are
+    floats = MT.ClipModel(tower, lib=inject(L, device))(images.float() / 255)  # [0,1] floats are taken as they are
     assert float((floats - out).abs().max()) <= 1e-4 * float(out.abs().max())
 
 
@@ -279,12 +271,12 @@ def write_images(directory, seed=0):
 def check_files(L, st, device, directory, decoder="pil"):
     names = write_images(directory)
     assert MT.list_image_files(directory) == names == ["a.JPG", "b.png", "c.jpeg", "d.PNG", "e.jpg"]
-    got = MT.load_images_299(directory, names, decoder=decoder, device=device, lib=_inject(L, device))
+    got = MT.load_images_299(directory, names, decoder=decoder, device=device, lib=inject(L, device))
     assert got.shape == (5, 3, 299, 299) and got.dtype == torch.uint8 and got.device.type == device.type
     for k, name in enumerate(names):
         ref = np.asarray(PIL.Image.open(os.path.join(directory, name)).resize((299, 299), PIL.Image.LANCZOS))
         assert np.array_equal(got[k].cpu().numpy().transpose(1, 2, 0), ref), name
-    assert MT.load_images_299(directory, [], device=device, lib=_inject(L, device)).shape == (0, 3, 299, 299)
+    assert MT.load_images_299(directory, [], device=device, lib=inject(L, device)).shape == (0, 3, 299, 299)
 
 
 def check_cli(L, st, device, root):
@@ -301,12 +293,12 @@ def check_cli(L, st, device, root):
     out = os.path.join(root, "logs", "metric.csv")
     argv = ["--source_dataset", dirs["real"], "--methods_dataset", f"A,{dirs['method_a']}", f"B,{dirs['method_b']}", "--output", out,
             "--batch", "2"]
-    fids = MT.main(argv, feature=feature, lib=_inject(L, device), device=device)
+    fids = MT.main(argv, feature=feature, lib=inject(L, device), device=device)
     assert list(fids) == ["A", "B"]
     want = {}
-    real = feature(MT.load_images_299(dirs["real"], MT.list_image_files(dirs["real"]), device=device, lib=_inject(L, device)))
+    real = feature(MT.load_images_299(dirs["real"], MT.list_image_files(dirs["real"]), device=device, lib=inject(L, device)))
     for name, key in (("A", "method_a"), ("B", "method_b")):
-        fake = feature(MT.load_images_299(dirs[key], MT.list_image_files(dirs[key]), device=device, lib=_inject(L, device)))
+        fake = feature(MT.load_images_299(dirs[key], MT.list_image_files(dirs[key]), device=device, lib=inject(L, device)))
         want[name] = R.fid_symmetric(*R.gaussian(real.cpu().numpy()), *R.gaussian(fake.cpu().numpy()))
         assert abs(fids[name] - want[name]) <= dist_threshold("deficient", 6) * max(1.0, abs(want[name])), (fids[name], want[name])
     with open(out, newline="") as f:
@@ -316,31 +308,22 @@ def check_cli(L, st, device, root):
 
 
 # ---- error paths --------------------------------------------------------------------------------------------------
-def _raises(kind, fn, text=None):
-    try:
-        fn()
-    except kind as e:
-        assert text is None or text in str(e), str(e)
-    else:
-        raise AssertionError(f"{kind.__name__} expected")
-
-
 def check_errors(L, st, device):
-    lib = _inject(L, device)
-    _raises(NotImplementedError, lambda: MT.FrechetDistance(2048), "Inception")
-    _raises(NotImplementedError, lambda: MT.FrechetDistance(feature=64))
+    lib = inject(L, device)
+    raises(NotImplementedError, lambda: MT.FrechetDistance(2048), "Inception")
+    raises(NotImplementedError, lambda: MT.FrechetDistance(feature=64))
     f = _dev(stat_features(67, 24), device)
     fid = MT.FrechetDistance(lambda x: x, lib=lib)
-    _raises(RuntimeError, fid.compute, "More than one sample")
+    raises(RuntimeError, fid.compute, "More than one sample")
     fid.update_features(f, real=True)
     fid.update_features(f[:1], real=False)
-    _raises(RuntimeError, fid.compute, "More than one sample")  # one sample on the fake side
-    _raises(ValueError, lambda: fid.update_features(_dev(stat_features(5, 3), device), real=False), "dimension")
-    _raises(ValueError, lambda: fid.update_features(f[0], real=False))
-    _raises(ValueError, lambda: MT.frechet_distance(torch.zeros(3, device=device), torch.eye(3, device=device),
-                                                    torch.zeros(4, device=device), torch.eye(4, device=device), lib=lib))
+    raises(RuntimeError, fid.compute, "More than one sample")  # one sample on the fake side
+    raises(ValueError, lambda: fid.update_features(_dev(stat_features(5, 3), device), real=False), "dimension")
+    raises(ValueError, lambda: fid.update_features(f[0], real=False))
+    raises(ValueError, lambda: MT.frechet_distance(torch.zeros(3, device=device), torch.eye(3, device=device),
+                                                   torch.zeros(4, device=device), torch.eye(4, device=device), lib=lib))
     dense = _dev(R.eig_matrix("spread", 24), device)
-    _raises(RuntimeError, lambda: M.sym_eigh_f64(L, st, dense, True, 1), "no convergence in 1 sweeps")
+    raises(RuntimeError, lambda: M.sym_eigh_f64(L, st, dense, True, 1), "no convergence in 1 sweeps")
     # the C entry points: a null or misaligned pointer is an invalid argument, and nothing is launched
     d = 8
     buf = torch.zeros(4 * d * d + 64, dtype=torch.float64, device=device)

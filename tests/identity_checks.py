@@ -28,7 +28,6 @@ Rules.
                  Device errors measured on the MI355X are recorded in DESIGN.md 4.28 with their ratios to these figures.
 """
 import functools
-import json
 import os
 
 import numpy as np
@@ -39,6 +38,7 @@ from hairfastgan_amd import _marshal as M
 from hairfastgan_amd import _runtime
 from hairfastgan_amd import identity as ID
 from tests import identity_ref as R
+from tests.metric_common import bits, inject, raises, read_scores
 
 U32 = R.U32
 EPS64 = 2.0 ** -53
@@ -60,27 +60,8 @@ SIM_MEASURED = {"full": 1.6e-7, "small": 1.0e-7, "tiny": 6.6e-8}
 FULL_PAIRS = (1, 2, 3, 0)                   # image i is compared with image FULL_PAIRS[i]
 
 
-def _inject(L, device):
-    """The `lib` argument of hairfastgan_amd.identity: the interpreter build on CPU tensors, the product's own library on the GPU."""
-    return L if device.type == "cpu" else None
-
-
-def _bits(t):
-    a = t.detach().cpu().contiguous().numpy()
-    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32)
-
-
 def _rng(*key):
     return np.random.default_rng([23] + [int(v) for v in key])
-
-
-def _raises(kind, fn, text=None):
-    try:
-        fn()
-    except kind as e:
-        assert text is None or text in str(e), str(e)
-    else:
-        raise AssertionError(f"{kind.__name__} expected")
 
 
 # ---- crop and pool ------------------------------------------------------------------------------------------------
@@ -137,8 +118,8 @@ def check_normalize(L, st, device, d):
     assert bool(((norms.cpu().double() - tn).abs() <= U32 * tn).all())
     for r in range(3):  # a row's bits do not depend on the number of rows
         one = M.l2_normalize_rows(L, st, x[r:r + 1].to(device))
-        assert np.array_equal(_bits(one), _bits(out[r:r + 1])), r
-    assert np.array_equal(_bits(M.l2_normalize_rows(L, st, x.to(device))), _bits(out))
+        assert np.array_equal(bits(one), bits(out[r:r + 1])), r
+    assert np.array_equal(bits(M.l2_normalize_rows(L, st, x.to(device))), bits(out))
     buf = torch.zeros(64, device=device)
     p = buf.data_ptr()
     assert L.hf_l2_normalize_rows_f32(p, None, p, 2, 5, st) == 0
@@ -154,15 +135,15 @@ def check_similarity(L, st, device):
         ta, tb = torch.from_numpy(a).to(device), torch.from_numpy(b).to(device)
         pair, full = M.row_similarity(L, st, ta, tb), M.row_similarity(L, st, ta, tb, paired=False)
         assert pair.shape == (3,) and full.shape == (3, 3) and pair.dtype == torch.float64
-        assert np.array_equal(_bits(pair), _bits(full.diagonal()))
-        assert np.array_equal(_bits(M.row_similarity(L, st, ta[1:2], tb[1:2])), _bits(pair[1:2]))   # N does not matter
-        assert np.array_equal(_bits(M.row_similarity(L, st, ta[2:], tb[:2], paired=False)), _bits(full[2:, :2]))  # nor M
+        assert np.array_equal(bits(pair), bits(full.diagonal()))
+        assert np.array_equal(bits(M.row_similarity(L, st, ta[1:2], tb[1:2])), bits(pair[1:2]))   # N does not matter
+        assert np.array_equal(bits(M.row_similarity(L, st, ta[2:], tb[:2], paired=False)), bits(full[2:, :2]))  # nor M
         a2, b5 = rng.standard_normal((2, d)).astype(np.float32), rng.standard_normal((5, d)).astype(np.float32)
         got = M.row_similarity(L, st, torch.from_numpy(a2).to(device), torch.from_numpy(b5).to(device), paired=False).cpu().numpy()
         mag = np.abs(a2.astype(np.float64)) @ np.abs(b5.astype(np.float64)).T
         err = np.abs(got - R.similarity(a2, b5, paired=False))
         assert got.shape == (2, 5) and (err <= 4 * d * EPS64 * mag).all(), float((err / mag).max() / EPS64)
-    _raises(ValueError, lambda: M.row_similarity(L, st, ta, tb[:2]))
+    raises(ValueError, lambda: M.row_similarity(L, st, ta, tb[:2]))
     buf = torch.zeros(64, dtype=torch.float64, device=device)
     p = buf.data_ptr()
     assert L.hf_row_similarity_f64(p, p, p, 2, 2, 5, 1, st) == 0 and L.hf_row_similarity_f64(p, p, p, 2, 3, 5, 0, st) == 0
@@ -213,7 +194,7 @@ def make_idloss(L, device, kind, models={}):
         units, size, crop, _, _ = _case(kind)
         net = ID.Backbone(size, units=units)
         net.load_state_dict(state(kind))
-        models[key] = ID.IDLoss(net.to(device), lib=_inject(L, device), crop=crop)
+        models[key] = ID.IDLoss(net.to(device), lib=inject(L, device), crop=crop)
     models[key].facenet.invalidate()  # the plan follows the precision mode of its first call
     return models[key]
 
@@ -237,7 +218,7 @@ def check_network(L, st, device, kind, every_row=True):
     assert serr <= thr_s, (kind, serr, thr_s)
     assert float((full.diagonal() - 1).abs().max()) <= 2.0 ** -22
     for i in range(x.shape[0] if every_row else 1):
-        assert np.array_equal(_bits(idl.extract_feats(x[i:i + 1])), _bits(got[i:i + 1])), i
+        assert np.array_equal(bits(idl.extract_feats(x[i:i + 1])), bits(got[i:i + 1])), i
     return got
 
 
@@ -264,7 +245,7 @@ def check_similarity_full(L, st, device):
     assert got.shape == (4,) and got.dtype == torch.float64 and err <= thr_s, (err, thr_s)
     same = idl.similarity(x, x.clone())
     assert float((same.cpu() - 1).abs().max()) <= 2.0 ** -22
-    assert np.array_equal(_bits(idl.extract_feats(x)), _bits(idl.extract_feats(x.clone())))
+    assert np.array_equal(bits(idl.extract_feats(x)), bits(idl.extract_feats(x.clone())))
     mat = idl.similarity_matrix(x[:2], x)
     assert mat.shape == (2, 4) and float((mat.cpu() - want[:2] @ want.T).abs().max()) <= thr_s
 
@@ -290,15 +271,15 @@ def check_forward(L, st, device, kind):
 
 def check_refusals():
     """What needs no kernel: depths, modes and sizes that are not built, images too small for the crop."""
-    _raises(NotImplementedError, lambda: ID.Backbone(112, 100, "ir_se"))
-    _raises(NotImplementedError, lambda: ID.Backbone(112, 50, "ir"))
-    _raises(ValueError, lambda: ID.Backbone(128, 50, "ir_se"), "112 or 224")
-    _raises(ValueError, lambda: ID.Backbone(30, units=list(SMALL_UNITS)))
+    raises(NotImplementedError, lambda: ID.Backbone(112, 100, "ir_se"))
+    raises(NotImplementedError, lambda: ID.Backbone(112, 50, "ir"))
+    raises(ValueError, lambda: ID.Backbone(128, 50, "ir_se"), "112 or 224")
+    raises(ValueError, lambda: ID.Backbone(30, units=list(SMALL_UNITS)))
     idl = ID.IDLoss(ID.Backbone(SMALL_SIZE, units=list(SMALL_UNITS)), lib=object())
-    _raises(ValueError, lambda: idl.extract_feats(torch.zeros(1, 3, 222, 256)), "crop")
-    _raises(ValueError, lambda: idl.extract_feats(torch.zeros(1, 3, 256, 219)), "crop")
-    _raises(ValueError, lambda: idl.extract_feats(torch.zeros(1, 1, 256, 256)))
-    _raises(ValueError, lambda: idl.similarity(torch.zeros(1, 3, 256, 256), torch.zeros(2, 3, 256, 256)))
+    raises(ValueError, lambda: idl.extract_feats(torch.zeros(1, 3, 222, 256)), "crop")
+    raises(ValueError, lambda: idl.extract_feats(torch.zeros(1, 3, 256, 219)), "crop")
+    raises(ValueError, lambda: idl.extract_feats(torch.zeros(1, 1, 256, 256)))
+    raises(ValueError, lambda: idl.similarity(torch.zeros(1, 3, 256, 256), torch.zeros(2, 3, 256, 256)))
 
 
 # ---- command line -------------------------------------------------------------------------------------------------
@@ -326,9 +307,9 @@ def check_cli(L, st, device, root, decoder="pil"):
     units, size = list(TINY_UNITS), TINY_SIZE
     net = ID.Backbone(size, units=units)
     net.load_state_dict(state("tiny"))
-    model = ID.IDLoss(net.to(device), lib=_inject(L, device), crop=CLI_CROP)
+    model = ID.IDLoss(net.to(device), lib=inject(L, device), crop=CLI_CROP)
     scores = ID.main(["--data_path", data, "--gt_path", gt, "--size", "32", "--batch", "2", "--image_decoder", decoder], model=model,
-                     lib=_inject(L, device), device=device)
+                     lib=inject(L, device), device=device)
     ref_net = R.network(state("tiny"), units, size)
 
     def load(folder):
@@ -336,17 +317,14 @@ def check_cli(L, st, device, root, decoder="pil"):
         return (torch.from_numpy(np.stack(arr)).permute(0, 3, 1, 2).double() / 255 - 0.5) / 0.5
 
     want = (R.extract_feats(ref_net, load(data), CLI_CROP) * R.extract_feats(ref_net, load(gt), CLI_CROP)).sum(1).tolist()
-    out = os.path.join(root, "inference_metrics")
-    with open(os.path.join(out, "scores_id.json")) as f:
-        saved = json.load(f)
+    saved, stat = read_scores(root, "id")
     assert list(saved) == list(CLI_FILES) == list(scores) and saved == scores
     thr_s = thresholds("tiny")[1]
     values = [saved[n] for n in CLI_FILES]
     print("cli similarities", values, want)
     assert all(abs(a - b) <= thr_s for a, b in zip(values, want)), (values, want)
     assert want[0] - want[2] > 0.01  # the noisier copy is less similar: the scores mean something
-    with open(os.path.join(out, "stat_id.txt")) as f:
-        assert f.read() == "Average similarity is {:.2f}+-{:.2f}".format(np.mean(values), np.std(values))
+    assert stat == "Average similarity is {:.2f}+-{:.2f}".format(np.mean(values), np.std(values))
     os.remove(os.path.join(gt, CLI_FILES[1]))
-    _raises(FileNotFoundError, lambda: ID.main(["--data_path", data, "--gt_path", gt, "--size", "32"], model=model, lib=_inject(L, device),
-                                               device=device), CLI_FILES[1])
+    raises(FileNotFoundError, lambda: ID.main(["--data_path", data, "--gt_path", gt, "--size", "32"], model=model, lib=inject(L, device),
+                                              device=device), CLI_FILES[1])

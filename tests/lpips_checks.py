@@ -29,7 +29,6 @@ Rules.
 tests/test_lpips_ref.py measures the recorded fp32 errors again and fails if one exceeds what is recorded here.
 """
 import functools
-import json
 import os
 
 import numpy as np
@@ -41,6 +40,7 @@ from hairfastgan_amd import _marshal as M
 from hairfastgan_amd import face_align as FA
 from hairfastgan_amd import lpips as LP
 from tests import lpips_ref as R
+from tests.metric_common import bits, inject, raises, read_scores
 
 EPS64 = 2.0 ** -52
 
@@ -56,15 +56,6 @@ LPIPS_GPU = (("alex", 272),)
 NOISES = (0.5, 1e-2, 1e-4)
 LPIPS_MEASURED = {("alex", 0.5): 1.5e-9, ("alex", 1e-2): 8.4e-12, ("alex", 1e-4): 3.2e-13,
                   ("vgg", 0.5): 6.2e-10, ("vgg", 1e-2): 4.8e-12, ("vgg", 1e-4): 7.2e-14}
-
-
-def _inject(L, device):
-    """The `lib` argument of hairfastgan_amd.lpips: the interpreter build on CPU tensors, the product's own library on the GPU."""
-    return L if device.type == "cpu" else None
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().numpy().view(np.uint64)
 
 
 def _seed(*key):
@@ -187,7 +178,7 @@ def check_layer(L, st, device, shape, family):
     assert bool((err <= thr).all()), (shape, family, err.tolist(), thr.tolist())
     if family == "zeroed":  # both maps all zero: 0 / 1e-10 - 0 / 1e-10
         z = torch.zeros_like(fx)
-        assert _bits(_layer(L, st, device, z, z, lin_w)).tolist() == [0] * shape[0]
+        assert bits(_layer(L, st, device, z, z, lin_w)).tolist() == [0] * shape[0]
 
 
 def check_layer_conditions(L, st, device, shape):
@@ -196,16 +187,16 @@ def check_layer_conditions(L, st, device, shape):
     fx, fy, lin_w = layer_case(shape, "independent")
     n = shape[0]
     d = _layer(L, st, device, fx, fy, lin_w)
-    assert _bits(_layer(L, st, device, fx, fx, lin_w)).tolist() == [0] * n
-    assert np.array_equal(_bits(_layer(L, st, device, fy, fx, lin_w)), _bits(d))
-    assert np.array_equal(_bits(_layer(L, st, device, fx, fy, lin_w)), _bits(d))
+    assert bits(_layer(L, st, device, fx, fx, lin_w)).tolist() == [0] * n
+    assert np.array_equal(bits(_layer(L, st, device, fy, fx, lin_w)), bits(d))
+    assert np.array_equal(bits(_layer(L, st, device, fx, fy, lin_w)), bits(d))
     for i in range(n):
-        assert np.array_equal(_bits(_layer(L, st, device, fx[i:i + 1], fy[i:i + 1], lin_w)), _bits(d[i:i + 1])), i
+        assert np.array_equal(bits(_layer(L, st, device, fx[i:i + 1], fy[i:i + 1], lin_w)), bits(d[i:i + 1])), i
     big = _layer(L, st, device, torch.cat([fy, fx.flip(0), fx]), torch.cat([fx, fy.flip(0), fy]), lin_w)
-    assert np.array_equal(_bits(big), np.concatenate([_bits(d), _bits(d.flip(0)), _bits(d)]))
+    assert np.array_equal(bits(big), np.concatenate([bits(d), bits(d.flip(0)), bits(d)]))
     start = torch.linspace(0.25, 1.75, n, dtype=torch.float64).to(device)
     acc = _layer(L, st, device, fx, fy, lin_w, into=start.clone())
-    assert np.array_equal(_bits(acc), _bits(start + d))
+    assert np.array_equal(bits(acc), bits(start + d))
 
 
 def check_layer_refusals(L, st, device):
@@ -241,7 +232,7 @@ def lpips_fp32_error(net_type, size, noise):
 
 
 def make_model(L, device, net_type):
-    model = LP.LPIPS(net_type, lib=_inject(L, device))
+    model = LP.LPIPS(net_type, lib=inject(L, device))
     model.load_state_dict(R.random_weights(net_type))
     return model.to(device).eval()
 
@@ -271,7 +262,7 @@ def check_lpips(L, st, device, net_type, size, whole_batch=False, shared_x=False
     else:
         got = model.per_sample(torch.cat([x] * 4).to(device), torch.cat(ys + [x]).to(device))
     assert got.shape == (3 if shared_x else 4,) and got.dtype == torch.float64 and got.device.type == device.type
-    assert _bits(got[3:]).tolist() == [0] * (got.numel() - 3)
+    assert bits(got[3:]).tolist() == [0] * (got.numel() - 3)
     for k, noise in enumerate(NOISES):
         truth, floor = (float(t[0]) for t in lpips_truth(net_type, size, noise))
         thr = max(8.0 * LPIPS_MEASURED[(net_type, noise)], floor)
@@ -290,7 +281,7 @@ def check_lpips(L, st, device, net_type, size, whole_batch=False, shared_x=False
 
 # ---- L2 / PSNR ----------------------------------------------------------------------------------------------------
 def check_psnr(L, st, device):
-    lib = _inject(L, device)
+    lib = inject(L, device)
     rng = np.random.default_rng(11)
     for shape in ((3, 3, 17, 23), (2, 3, 64, 65), (1, 1, 1, 1)):
         a, b = rng.integers(0, 256, shape, dtype=np.uint8), rng.integers(0, 256, shape, dtype=np.uint8)
@@ -298,42 +289,33 @@ def check_psnr(L, st, device):
         ta, tb = torch.from_numpy(a).to(device), torch.from_numpy(b).to(device)
         sums = M.sq_err_sum(L, st, ta, tb)
         want = R.sq_err_sum(a, b)
-        assert np.array_equal(_bits(sums), want.astype(np.float64).view(np.uint64)), shape
-        assert np.array_equal(_bits(LP.mse(ta, tb, lib=lib)), (want.astype(np.float64) / per).view(np.uint64))
+        assert np.array_equal(bits(sums), want.astype(np.float64).view(np.uint64)), shape
+        assert np.array_equal(bits(LP.mse(ta, tb, lib=lib)), (want.astype(np.float64) / per).view(np.uint64))
         got = LP.psnr(ta, tb, lib=lib).cpu().numpy()
         ref = R.psnr(a, b, 255)
         assert np.all(np.abs(got - ref) <= 4 * EPS64 * np.abs(ref) + 10 * EPS64), (got, ref)
         assert np.all(np.isinf(LP.psnr(ta, ta, lib=lib).cpu().numpy()))
         for i in range(shape[0]):  # batch invariance
-            assert np.array_equal(_bits(M.sq_err_sum(L, st, ta[i:i + 1], tb[i:i + 1])), _bits(sums[i:i + 1]))
+            assert np.array_equal(bits(M.sq_err_sum(L, st, ta[i:i + 1], tb[i:i + 1])), bits(sums[i:i + 1]))
         fa, fb = rng.standard_normal(shape).astype(np.float32), rng.standard_normal(shape).astype(np.float32)
         fta, ftb = torch.from_numpy(fa).to(device), torch.from_numpy(fb).to(device)
         fs = M.sq_err_sum(L, st, fta, ftb)
         fw = R.sq_err_sum(fa, fb)
         assert np.all(np.abs(fs.cpu().numpy() - fw) <= per * EPS64 * fw), shape
         for i in range(shape[0]):
-            assert np.array_equal(_bits(M.sq_err_sum(L, st, fta[i:i + 1], ftb[i:i + 1])), _bits(fs[i:i + 1]))
+            assert np.array_equal(bits(M.sq_err_sum(L, st, fta[i:i + 1], ftb[i:i + 1])), bits(fs[i:i + 1]))
         assert np.all(np.isinf(LP.psnr(fta, fta, data_range=2.0, lib=lib).cpu().numpy()))
         p2 = LP.psnr(fta, ftb, data_range=2.0, lib=lib).cpu().numpy()
         r2 = R.psnr(fa, fb, 2.0)
         assert np.all(np.abs(p2 - r2) <= 4 * EPS64 * np.abs(r2) + 10 * (per + 1) * EPS64)
-    _raises(ValueError, lambda: LP.psnr(fta, ftb, lib=lib), "data_range")
-    _raises(ValueError, lambda: M.sq_err_sum(L, st, ta, ftb))
+    raises(ValueError, lambda: LP.psnr(fta, ftb, lib=lib), "data_range")
+    raises(ValueError, lambda: M.sq_err_sum(L, st, ta, ftb))
     buf = torch.zeros(64, dtype=torch.float64, device=device)
     p = buf.data_ptr()
     assert L.hf_sq_err_sum_work_doubles(2, 12480) == 8 and L.hf_sq_err_sum_work_doubles(1, 1) == 1
     for args in ((None, p, p, p, 1, 4, 0), (p + 4, p, p, p, 1, 4, 0), (p, None, p, p, 1, 4, 1), (p, p + 1, p, p, 1, 4, 0), (p, p, p, None, 1, 4, 0),
                  (p, p, p, p, 0, 4, 0), (p, p, p, p, 1, 0, 0)):
         assert L.hf_sq_err_sum_f64(*args, st) == -1, args
-
-
-def _raises(kind, fn, text=None):
-    try:
-        fn()
-    except kind as e:
-        assert text is None or text in str(e), str(e)
-    else:
-        raise AssertionError(f"{kind.__name__} expected")
 
 
 # ---- command line -------------------------------------------------------------------------------------------------
@@ -356,7 +338,7 @@ def write_pairs(root):
 def check_cli(L, st, device, root, decoder="pil"):
     """Six small PNGs: the JSON keys are the file names, the values equal direct calls, the stat text has the reference's format."""
     data, gt = write_pairs(root)
-    lib = _inject(L, device)
+    lib = inject(L, device)
     names = [n for n, _ in CLI_FILES]
     model = make_model(L, device, "alex")
     res, truth = LP.load_pairs(data, gt, names, 64, decoder, device, lib)
@@ -369,12 +351,9 @@ def check_cli(L, st, device, root, decoder="pil"):
     for mode in ("lpips", "l2", "psnr"):
         scores = LP.main(["--mode", mode, "--data_path", data, "--gt_path", gt, "--size", "64", "--batch", "4", "--image_decoder", decoder],
                          model=model, lib=lib, device=device)
-        out = os.path.join(root, "inference_metrics")
-        with open(os.path.join(out, f"scores_{mode}.json")) as f:
-            saved = json.load(f)
+        saved, stat = read_scores(root, mode)
         assert list(saved) == names == list(scores)
         values = want[mode].cpu().tolist()
         assert [saved[n] for n in names] == values, mode
-        with open(os.path.join(out, f"stat_{mode}.txt")) as f:
-            assert f.read() == "Average loss is {:.2f}+-{:.2f}".format(np.mean(values), np.std(values))
+        assert stat == "Average loss is {:.2f}+-{:.2f}".format(np.mean(values), np.std(values))
     assert want["lpips"].min() > 0 and len(set(want["lpips"].tolist())) == 6

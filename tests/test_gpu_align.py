@@ -12,16 +12,9 @@ import torch
 
 from tests import align_checks as K
 from tests import align_ref as R
+from tests.metric_common import gpu_ctx
 
 pytestmark = pytest.mark.gpu
-
-
-def _ctx():
-    from hairfastgan_amd import _runtime
-
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU")
-    return _runtime.lib(), _runtime.stream(), torch.device("cuda:0")
 
 
 @functools.lru_cache(maxsize=None)
@@ -31,16 +24,16 @@ def _inputs(group, name):
 
 @pytest.mark.parametrize("in_w,in_h,out_w,out_h", K.RESIZE_CASES)
 def test_resize_lanczos(in_w, in_h, out_w, out_h):
-    K.check_resize(*_ctx(), in_w, in_h, out_w, out_h)
+    K.check_resize(*gpu_ctx(), in_w, in_h, out_w, out_h)
 
 
 @pytest.mark.parametrize("name", list(K.QUADS))
 def test_quad_transform(name):
-    K.check_transform(*_ctx(), name)
+    K.check_transform(*gpu_ctx(), name)
 
 
 def test_fused_equals_chained_pair_256_to_64():
-    K.check_fused_small(*_ctx())
+    K.check_fused_small(*gpu_ctx())
 
 
 def test_fused_equals_chained_pair_4096_to_1024(golden):
@@ -48,7 +41,7 @@ def test_fused_equals_chained_pair_4096_to_1024(golden):
     reference's result."""
     from hairfastgan_amd import face_align as FA
 
-    L, st, dev = _ctx()
+    L, st, dev = gpu_ctx()
     arr, lm = _inputs("golden", "inside")
     stages = {}
     fused = FA.align_bytes(L, st, K.chw(arr, dev), lm, fused=True, stages=stages)
@@ -64,9 +57,9 @@ def test_fused_equals_chained_pair_4096_to_1024(golden):
 
 @pytest.mark.parametrize("name", list(K.PAD_CASES))
 def test_pad(name):
-    K.check_pad(*_ctx(), name)
+    K.check_pad(*gpu_ctx(), name)
     if name == "none":
-        K.check_pad_invalid(*_ctx())
+        K.check_pad_invalid(*gpu_ctx())
 
 
 @pytest.mark.parametrize("name", list(R.GOLDEN_CASES))
@@ -74,7 +67,7 @@ def test_align_face_golden(golden, name):
     """align_face at the reference's sizes against the reference's own result (a 128^2 crop and the every-8th-pixel grid)."""
     from hairfastgan_amd import face_align as FA
 
-    L, st, dev = _ctx()
+    L, st, dev = gpu_ctx()
     G = golden("align.npz")
     arr, lm = _inputs("golden", name)
     stages = {}
@@ -102,14 +95,14 @@ def test_align_face_golden(golden, name):
 def test_align_small_against_restatement(name):
     """The three geometries at output 64 / transform 256, every stage against the restatement; `inside` enters as a float
     tensor (the truncating byte conversion of ToPILImage)."""
-    K.check_align_against_restatement(*_ctx(), R.SMALL_CASES[name], 64, 256,
+    K.check_align_against_restatement(*gpu_ctx(), R.SMALL_CASES[name], 64, 256,
                                       count_key="small_corner" if name == "corner" else None, as_float=name == "inside")
 
 
 def test_align_face_list_of_three_sizes():
     from hairfastgan_amd import face_align as FA
 
-    L, st, dev = _ctx()
+    L, st, dev = gpu_ctx()
     names = ["inside", "corner of a 140 x 110 image", "shrink"]
     pairs = [_inputs("small", "inside"), R.case_inputs((140, 110, 25, (24, 22, 20, 7.0))), _inputs("small", "shrink")]
     assert len({p[0].shape for p in pairs}) == 3
@@ -130,7 +123,7 @@ def test_swap_align_true():
     from hairfastgan_amd import face_align as FA
     from tests.test_gpu_schedule import _hairfast
 
-    _, _, dev = _ctx()
+    _, _, dev = gpu_ctx()
     hf = _hairfast(dev)
     cases = [R.GOLDEN_CASES["inside"], R.GOLDEN_CASES["corner"], (640, 480, 17, (330, 200, 70, -11.0))]
     pairs = [R.case_inputs(c) for c in cases]

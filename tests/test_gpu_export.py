@@ -6,16 +6,9 @@ import pytest
 import torch
 
 from tests import export_checks as K
+from tests.metric_common import gpu_ctx
 
 pytestmark = pytest.mark.gpu
-
-
-def _ctx():
-    from hairfastgan_amd import _runtime
-
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU")
-    return _runtime.lib(), _runtime.stream(), torch.device("cuda:0")
 
 
 @pytest.mark.parametrize("layout", ["hwc", "chw"])
@@ -23,24 +16,24 @@ def _ctx():
 @pytest.mark.parametrize("value_range", K.RANGES)
 @pytest.mark.parametrize("shape", K.SHAPES)
 def test_to_bytes(shape, value_range, rounding, layout):
-    K.check_to_bytes(*_ctx(), shape, value_range, rounding, layout)
+    K.check_to_bytes(*gpu_ctx(), shape, value_range, rounding, layout)
 
 
 def test_to_bytes_unaligned_base():
-    K.check_to_bytes_unaligned(*_ctx())
+    K.check_to_bytes_unaligned(*gpu_ctx())
 
 
 def test_to_bytes_general_range():
-    K.check_general_range(*_ctx())
+    K.check_general_range(*gpu_ctx())
 
 
 def test_labels_to_rgb():
-    K.check_labels_to_rgb(*_ctx())
+    K.check_labels_to_rgb(*gpu_ctx())
     K.check_palette_is_the_goldens()
 
 
 def test_invalid_arguments():
-    K.check_invalid(*_ctx())
+    K.check_invalid(*gpu_ctx())
 
 
 def test_public_functions(tmp_path):
@@ -50,7 +43,7 @@ def test_public_functions(tmp_path):
 
     from hairfastgan_amd import image_utils as IU
 
-    _, _, dev = _ctx()
+    _, _, dev = gpu_ctx()
     x = next(K.chunks((2, 3, 8, 12)))
     for value_range in K.RANGES:
         for rounding in IU.ROUNDINGS:

@@ -7,50 +7,42 @@ import subprocess
 import sys
 
 import pytest
-import torch
 
 from tests import frechet_checks as K
 from tests import frechet_ref as R
+from tests.metric_common import gpu_ctx
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _ctx():
-    from hairfastgan_amd import _runtime
-
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU")
-    return _runtime.lib(), _runtime.stream(), torch.device("cuda:0")
-
-
 @pytest.mark.parametrize("n,d", K.ACCUMULATE_SHAPES)
 def test_accumulate(n, d):
-    K.check_accumulate(*_ctx(), n, d)
+    K.check_accumulate(*gpu_ctx(), n, d)
 
 
 def test_accumulate_split():
-    K.check_accumulate_split(*_ctx())
+    K.check_accumulate_split(*gpu_ctx())
 
 
 def test_accumulate_f16():
-    K.check_accumulate_f16(*_ctx())
+    K.check_accumulate_f16(*gpu_ctx())
 
 
 def test_reset():
-    K.check_reset(*_ctx())
+    K.check_reset(*gpu_ctx())
 
 
 @pytest.mark.parametrize("d", K.EIG_SIZES)
 @pytest.mark.parametrize("family", R.EIG_FAMILIES)
 def test_eigh(family, d):
-    K.check_eigh(*_ctx(), family, d)
+    K.check_eigh(*gpu_ctx(), family, d)
 
 
 @pytest.mark.parametrize("case", list(K.DIST_CASES))
 def test_distance(case):
-    K.check_distance(*_ctx(), *case, K.DIST_CASES[case])
+    K.check_distance(*gpu_ctx(), *case, K.DIST_CASES[case])
 
 
 def test_size_512_under_a_time_limit():
@@ -70,17 +62,17 @@ def test_size_512_under_a_time_limit():
 
 
 def test_clip_model():
-    K.check_clip_model(*_ctx())
+    K.check_clip_model(*gpu_ctx())
 
 
 @pytest.mark.parametrize("decoder", ["pil", "device"])
 def test_files(tmp_path, decoder):
-    K.check_files(*_ctx(), str(tmp_path), decoder)
+    K.check_files(*gpu_ctx(), str(tmp_path), decoder)
 
 
 def test_cli(tmp_path):
-    K.check_cli(*_ctx(), str(tmp_path))
+    K.check_cli(*gpu_ctx(), str(tmp_path))
 
 
 def test_errors():
-    K.check_errors(*_ctx())
+    K.check_errors(*gpu_ctx())

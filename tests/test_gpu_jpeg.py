@@ -11,57 +11,50 @@ import torch
 
 from tests import jpeg_checks as K
 from tests import jpeg_ref as R
+from tests.metric_common import gpu_ctx
 
 pytestmark = pytest.mark.gpu
-
-
-def _ctx():
-    from hairfastgan_amd import _runtime
-
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU")
-    return _runtime.lib(), _runtime.stream(), torch.device("cuda:0")
 
 
 @pytest.mark.parametrize("mode", K.MODES, ids=str)
 @pytest.mark.parametrize("shape", K.SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_tiny_and_ragged(shape, mode):
-    K.check_tiny(*_ctx(), shape, mode)
+    K.check_tiny(*gpu_ctx(), shape, mode)
 
 
 def test_restart_index_wraps():
-    K.check_restart_wrap(*_ctx())
+    K.check_restart_wrap(*gpu_ctx())
 
 
 def test_chunk_boundary():
-    K.check_chunk_boundary(*_ctx())
+    K.check_chunk_boundary(*gpu_ctx())
 
 
 def test_symbol_coverage():
-    K.check_symbols(*_ctx())
+    K.check_symbols(*gpu_ctx())
 
 
 def test_bound_holds_for_noise():
-    K.check_bound(*_ctx())
+    K.check_bound(*gpu_ctx())
 
 
 def test_batch_invariant_and_deterministic():
-    K.check_batch_invariance(*_ctx())
+    K.check_batch_invariance(*gpu_ctx())
 
 
 def test_invalid_arguments():
-    K.check_invalid(*_ctx())
+    K.check_invalid(*gpu_ctx())
 
 
 def test_marshalled_call():
-    K.check_marshalled(*_ctx())
+    K.check_marshalled(*gpu_ctx())
 
 
 def test_encode_jpeg_shapes():
     """Every input form of encode_jpeg; a single image comes back as bytes; the arguments reach the file."""
     from hairfastgan_amd import image_utils as IU
 
-    _, _, dev = _ctx()
+    _, _, dev = gpu_ctx()
     rgb = np.stack([K.smooth((19, 21, 3), k) for k in range(2)])
     grey = rgb[..., 0]
     t = torch.from_numpy
@@ -102,7 +95,7 @@ def test_save_image_and_save_images_jpeg(tmp_path):
     from hairfastgan_amd import image_utils as IU
     from tests import png_checks as PK
 
-    _, _, dev = _ctx()
+    _, _, dev = gpu_ctx()
     rng = np.random.default_rng(0)
     one = torch.from_numpy(rng.random((1, 3, 40, 72), dtype=np.float32)).to(dev)
     many = torch.from_numpy(rng.random((3, 3, 40, 72), dtype=np.float32) * 2 - 1).to(dev)
@@ -150,7 +143,7 @@ def test_encode_jpeg_of_paste_back():
     from hairfastgan_amd import image_utils as IU
     from tests import align_ref as AR
 
-    _, _, dev = _ctx()
+    _, _, dev = gpu_ctx()
     photo, lm = AR.image(128, 96, 41), AR.landmarks(64, 44, 16, 7.0)
     result = np.random.default_rng(5).integers(0, 256, (64, 64, 3), dtype=np.uint8)
     pasted = FA.paste_back(photo, PIL.Image.fromarray(result, "RGB"), lm, output_size=64, return_tensors=False, device=dev)

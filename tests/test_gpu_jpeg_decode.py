@@ -7,20 +7,13 @@ import pytest
 import torch
 
 from tests import jpeg_decode_checks as K
+from tests.metric_common import gpu_ctx
 
 pytestmark = pytest.mark.gpu
 
 
-def _ctx():
-    from hairfastgan_amd import _runtime
-
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU")
-    return _runtime.lib(), _runtime.stream(), torch.device("cuda:0")
-
-
 def test_entry_points_are_bound():
-    L, _, _ = _ctx()
+    L, _, _ = gpu_ctx()
     assert L.hf_abi_version() == 13
     assert L.hf_jpeg_decode_workspace_bytes(1, 8, 8, 1, 1, 1, 0, 100) == 128 + 64 + 16
 
@@ -28,43 +21,43 @@ def test_entry_points_are_bound():
 @pytest.mark.parametrize("mode", K.MODES, ids=str)
 @pytest.mark.parametrize("shape", K.SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_shapes_modes_qualities(shape, mode):
-    K.check_grid(*_ctx(), shape, mode)
+    K.check_grid(*gpu_ctx(), shape, mode)
 
 
 def test_several_windows():
-    K.check_windows(*_ctx())
+    K.check_windows(*gpu_ctx())
 
 
 def test_flat_and_checkerboard():
-    K.check_flat(*_ctx())
+    K.check_flat(*gpu_ctx())
 
 
 def test_stuffed_bytes_at_boundaries():
-    K.check_stuffing(*_ctx())
+    K.check_stuffing(*gpu_ctx())
 
 
 def test_custom_tables_and_extreme_coefficients():
-    K.check_custom_tables(*_ctx())
+    K.check_custom_tables(*gpu_ctx())
 
 
 def test_restart_intervals():
-    K.check_restart(*_ctx())
+    K.check_restart(*gpu_ctx())
 
 
 def test_batch_invariant_and_deterministic():
-    K.check_batch(*_ctx())
+    K.check_batch(*gpu_ctx())
 
 
 def test_float_output():
-    K.check_float(*_ctx())
+    K.check_float(*gpu_ctx())
 
 
 def test_invalid_arguments():
-    K.check_invalid(*_ctx())
+    K.check_invalid(*gpu_ctx())
 
 
 def test_marshalled_call():
-    K.check_marshalled(*_ctx())
+    K.check_marshalled(*gpu_ctx())
 
 
 def _pil_rgb(data):
@@ -81,7 +74,7 @@ def test_decode_jpeg_forms(tmp_path):
     form is the CPU's byte / 255; unsupported and corrupt files raise ValueError."""
     from hairfastgan_amd import image_utils as IU
 
-    _, _, dev = _ctx()
+    _, _, dev = gpu_ctx()
     files = [K.pil_file(K.picture((37, 53), 2, 1), 75, 2), K.pil_file(K.picture((24, 40), 0, 2), 90, 0),
              K.pil_file(K.picture((37, 53), 2, 3), 75, 2), K.pil_file(K.picture((17, 9), "grey"), 75, "grey"),
              K.pil_file(K.picture((37, 53), 2, 4), 75, 2, restart_marker_rows=1), K.pil_file(K.noise((37, 53, 3), 5), 100, 2, optimize=True)]
@@ -125,7 +118,7 @@ def test_encode_jpeg_round_trip():
     from it, at every subsampling, for an image wider than one chunk of the encoder"""
     from hairfastgan_amd import image_utils as IU
 
-    _, _, dev = _ctx()
+    _, _, dev = gpu_ctx()
     imgs = torch.from_numpy(np.stack([K.picture((96, 700), 0, k) for k in range(2)])).to(dev)
     for name in IU.JPEG_SUBSAMPLINGS:
         files = IU.encode_jpeg(imgs, quality=90, subsampling=name)

@@ -9,33 +9,26 @@ import torch
 from tests import align_ref as R
 from tests import paste_checks as K
 from tests import paste_ref as PR
+from tests.metric_common import gpu_ctx
 
 pytestmark = pytest.mark.gpu
 
 
-def _ctx():
-    from hairfastgan_amd import _runtime
-
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU")
-    return _runtime.lib(), _runtime.stream(), torch.device("cuda:0")
-
-
 @pytest.mark.parametrize("name", list(K.CASES))
 def test_paste(name):
-    K.check_paste(*_ctx(), name)
+    K.check_paste(*gpu_ctx(), name)
 
 
 def test_paste_user_mask_without_feather():
-    K.check_paste(*_ctx(), "down", feather=0.0, with_mask=True)
+    K.check_paste(*gpu_ctx(), "down", feather=0.0, with_mask=True)
 
 
 def test_multiply_all_byte_pairs():
-    K.check_multiply(*_ctx())
+    K.check_multiply(*gpu_ctx())
 
 
 def test_invalid_arguments():
-    K.check_paste_invalid(*_ctx())
+    K.check_paste_invalid(*gpu_ctx())
 
 
 def test_paste_back_three_sizes():
@@ -43,7 +36,7 @@ def test_paste_back_three_sizes():
     three forms a result takes (float tensor, uint8 tensor, PIL image) - against the restatement; then one by one."""
     from hairfastgan_amd import face_align as FA
 
-    _, _, dev = _ctx()
+    _, _, dev = gpu_ctx()
     names = ["up", "rot30", "corner of a 140 x 110 photograph"]
     S = 64
     F = K.inputs("up")[1]
@@ -82,7 +75,7 @@ def test_swap_paste_back():
     from hairfastgan_amd import face_align as FA
     from tests.test_gpu_schedule import _hairfast
 
-    _, _, dev = _ctx()
+    _, _, dev = gpu_ctx()
     hf = _hairfast(dev)
     cases = [R.GOLDEN_CASES["inside"], R.GOLDEN_CASES["corner"], (640, 480, 17, (330, 200, 70, -11.0))]
     pairs = [R.case_inputs(c) for c in cases]

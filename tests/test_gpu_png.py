@@ -6,69 +6,62 @@ import pytest
 import torch
 
 from tests import png_checks as K
+from tests.metric_common import gpu_ctx
 
 pytestmark = pytest.mark.gpu
 
 
-def _ctx():
-    from hairfastgan_amd import _runtime
-
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU")
-    return _runtime.lib(), _runtime.stream(), torch.device("cuda:0")
-
-
 @pytest.mark.parametrize("shape", K.TINY)
 def test_tiny_and_ragged(shape):
-    K.check_tiny(*_ctx(), shape)
+    K.check_tiny(*gpu_ctx(), shape)
 
 
 def test_heights_around_a_segment():
-    K.check_heights(*_ctx())
+    K.check_heights(*gpu_ctx())
 
 
 def test_input_base_offset_by_one_byte():
-    K.check_offset_base(*_ctx())
+    K.check_offset_base(*gpu_ctx())
 
 
 @pytest.mark.parametrize("mode", [0, 1, 2, 3])
 def test_filter_modes(mode):
-    K.check_filter(*_ctx(), mode)
+    K.check_filter(*gpu_ctx(), mode)
 
 
 def test_runs():
-    K.check_runs(*_ctx())
+    K.check_runs(*gpu_ctx())
 
 
 def test_incompressible_takes_stored_blocks():
-    K.check_incompressible(*_ctx())
+    K.check_incompressible(*gpu_ctx())
 
 
 def test_deep_code_is_length_limited():
-    K.check_deep_code(*_ctx())
+    K.check_deep_code(*gpu_ctx())
 
 
 def test_batch_invariant_and_deterministic():
-    K.check_batch_invariance(*_ctx())
+    K.check_batch_invariance(*gpu_ctx())
 
 
 def test_size_conditions():
-    K.check_sizes(*_ctx())
+    K.check_sizes(*gpu_ctx())
 
 
 def test_invalid_arguments():
-    K.check_invalid(*_ctx())
+    K.check_invalid(*gpu_ctx())
 
 
 def test_marshalled_call():
-    K.check_marshalled(*_ctx())
+    K.check_marshalled(*gpu_ctx())
 
 
 def test_encode_png_shapes():
     """Every input form of encode_png; a single image comes back as bytes."""
     from hairfastgan_amd import image_utils as IU
 
-    _, _, dev = _ctx()
+    _, _, dev = gpu_ctx()
     rgb = np.stack([K.smooth((9, 21, 3), k) for k in range(2)])
     grey = rgb[..., 0]
     t = torch.from_numpy
@@ -97,7 +90,7 @@ def test_save_image_and_save_images(tmp_path):
     """save_image(encoder="device") and save_images on floats: the files decode to to_bytes(...)."""
     from hairfastgan_amd import image_utils as IU
 
-    _, _, dev = _ctx()
+    _, _, dev = gpu_ctx()
     rng = np.random.default_rng(0)
     one = torch.from_numpy(rng.random((1, 3, 64, 96), dtype=np.float32)).to(dev)
     many = torch.from_numpy(rng.random((3, 3, 64, 96), dtype=np.float32) * 2 - 1).to(dev)
@@ -130,7 +123,7 @@ def test_save_all_recorder_device_encoder(tmp_path):
     encoder writes the same file set as the PIL one, and every file decodes to the same pixels."""
     from hairfastgan_amd.hair_swap import SaveAllRecorder
 
-    _, _, dev = _ctx()
+    _, _, dev = gpu_ctx()
     g = torch.Generator().manual_seed(0)
     I_blend = (torch.rand(1, 3, 64, 96, generator=g) * 2 - 1).to(dev)
     I_final = (torch.rand(1, 3, 64, 96, generator=g) * 2 - 1).to(dev)

@@ -7,20 +7,13 @@ import pytest
 import torch
 
 from tests import png_decode_checks as K
+from tests.metric_common import gpu_ctx
 
 pytestmark = pytest.mark.gpu
 
 
-def _ctx():
-    from hairfastgan_amd import _runtime
-
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU")
-    return _runtime.lib(), _runtime.stream(), torch.device("cuda:0")
-
-
 def test_entry_points_are_bound():
-    L, _, _ = _ctx()
+    L, _, _ = gpu_ctx()
     assert L.hf_abi_version() == 13
     assert L.hf_png_decode_workspace_bytes(1, 1, 1, 0, 100) > 0
 
@@ -28,55 +21,55 @@ def test_entry_points_are_bound():
 @pytest.mark.parametrize("color_type", K.COLOR_TYPES, ids=lambda c: f"type{c}")
 @pytest.mark.parametrize("shape", K.SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_shapes_colour_types_levels(shape, color_type):
-    K.check_grid(*_ctx(), shape, color_type)
+    K.check_grid(*gpu_ctx(), shape, color_type)
 
 
 def test_every_filter_type():
-    K.check_filters(*_ctx())
+    K.check_filters(*gpu_ctx())
 
 
 def test_palettes():
-    K.check_palette(*_ctx())
+    K.check_palette(*gpu_ctx())
 
 
 def test_idat_structure():
-    K.check_idat_structure(*_ctx())
+    K.check_idat_structure(*gpu_ctx())
 
 
 def test_matches():
-    K.check_matches(*_ctx())
+    K.check_matches(*gpu_ctx())
 
 
 def test_hand_assembled_dynamic_block():
-    K.check_hand_block(*_ctx())
+    K.check_hand_block(*gpu_ctx())
 
 
 def test_segments_of_the_projects_encoder():
-    K.check_encoder_files(*_ctx())
+    K.check_encoder_files(*gpu_ctx())
 
 
 def test_full_and_sync_flushes():
-    K.check_flushes(*_ctx())
+    K.check_flushes(*gpu_ctx())
 
 
 def test_false_candidates():
-    K.check_false_candidates(*_ctx())
+    K.check_false_candidates(*gpu_ctx())
 
 
 def test_batch_invariant_and_deterministic():
-    K.check_batch(*_ctx())
+    K.check_batch(*gpu_ctx())
 
 
 def test_float_output():
-    K.check_float(*_ctx())
+    K.check_float(*gpu_ctx())
 
 
 def test_invalid_arguments():
-    K.check_invalid(*_ctx())
+    K.check_invalid(*gpu_ctx())
 
 
 def test_marshalled_call():
-    K.check_marshalled(*_ctx())
+    K.check_marshalled(*gpu_ctx())
 
 
 def test_decode_png_forms(tmp_path):
@@ -84,7 +77,7 @@ def test_decode_png_forms(tmp_path):
     the list; the float form is the CPU's byte / 255; unsupported files raise ValueError."""
     from hairfastgan_amd import image_utils as IU
 
-    _, _, dev = _ctx()
+    _, _, dev = gpu_ctx()
     files = [K.pil_file(K.picture((37, 53), 3, 1), 2), K.pil_file(K.picture((24, 40), 4, 2), 6, 9),
              K.pil_file(K.picture((37, 53), 3, 3), 2, 1), K.pil_file(K.picture((17, 9), 1), 0),
              K.pil_file(K.noise((37, 53, 1), 4), 3), K.pil_file(K.noise((37, 53, 2), 5), 4, 0), K.flush_files()[0], K.flush_files()[1]]
@@ -130,7 +123,7 @@ def test_encode_png_round_trip():
     several segments"""
     from hairfastgan_amd import image_utils as IU
 
-    _, _, dev = _ctx()
+    _, _, dev = gpu_ctx()
     imgs = torch.from_numpy(np.stack([K.picture((96, 700), 3, k) for k in range(2)])).to(dev)
     files = IU.encode_png(imgs)
     for data, img, src in zip(files, IU.decode_png(files), imgs):

@@ -2,7 +2,6 @@
 package is an un-vendored dependency): the oracle restatement against an assembly of torch's own nn.MultiheadAttention /
 nn.LayerNorm / nn.Conv2d modules in the published ViT arrangement, the product's state-dict layout, and - kernel sources
 interpreted by tests/hipsim - the HIP-path tower on a scaled-down configuration against the oracle."""
-import sys
 
 import pytest
 import torch
@@ -12,6 +11,7 @@ from hairfastgan_amd import _marshal as M
 from oracle import cases as C
 from oracle import ref_clip as RC
 from oracle import synth
+from tests.metric_common import patch_host_modules
 
 SMALL = dict(width=128, layers=2, patch=16, res=64, out_dim=32)
 
@@ -126,11 +126,7 @@ def sim_clip(simlib, monkeypatch):
 
     import hairfastgan_amd.encoders  # noqa: F401
 
-    for n in ("hairfastgan_amd.clip_vit", "hairfastgan_amd.encoders._fused"):
-        mod = sys.modules[n]
-        monkeypatch.setattr(mod, "lib", lambda: simlib)
-        monkeypatch.setattr(mod, "stream", lambda: None)
-        monkeypatch.setattr(mod, "require_gpu", lambda *a: None)
+    patch_host_modules(monkeypatch, simlib, ["hairfastgan_amd.clip_vit", "hairfastgan_amd.encoders._fused"])
     return simlib
 
 

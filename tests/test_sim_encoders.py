@@ -9,6 +9,7 @@ import torch.nn.functional as F
 from hairfastgan_amd import _marshal as M
 from oracle import cases as C
 from oracle import ref_encoders as E
+from tests.metric_common import patch_host_modules
 
 TOL = 2e-5
 
@@ -21,13 +22,10 @@ def maxdiff(a, b):
 def sim_backend(simlib, monkeypatch):
     import hairfastgan_amd.encoders  # noqa: F401
 
-    mods = [sys.modules[n] for n in ("hairfastgan_amd.encoders._fused", "hairfastgan_amd.encoders.e4e",
-                                     "hairfastgan_amd.encoders.fs_encoder", "hairfastgan_amd.encoders.post_process")]
-    for mod in mods:
-        monkeypatch.setattr(mod, "lib", lambda: simlib)
-        monkeypatch.setattr(mod, "stream", lambda: None)
-        monkeypatch.setattr(mod, "require_gpu", lambda *a: None)
-    return mods
+    names = ("hairfastgan_amd.encoders._fused", "hairfastgan_amd.encoders.e4e", "hairfastgan_amd.encoders.fs_encoder",
+             "hairfastgan_amd.encoders.post_process")
+    patch_host_modules(monkeypatch, simlib, names)
+    return [sys.modules[n] for n in names]
 
 
 @pytest.mark.parametrize("k,stride,B,cin,cout,H,W", [(3, 2, 2, 16, 24, 9, 13), (1, 2, 1, 12, 40, 10, 7), (1, 1, 3, 8, 8, 5, 5),

@@ -1,12 +1,12 @@
 """hipsim tests of the identity-similarity kernels (csrc/identity.h) and their host mirror (hairfastgan_amd.identity): the
 product's kernel sources interpreted on the CPU against the torch / numpy restatements (tests/identity_ref.py) by the checks of
 tests/identity_checks.py.  The network is two units at 28^2 (planes 28, 14 and 7) here; IR-SE50 at 112^2 runs on the GPU."""
-import sys
 
 import pytest
 import torch
 
 from tests import identity_checks as K
+from tests.metric_common import patch_host_modules
 
 CPU = torch.device("cpu")
 
@@ -16,11 +16,7 @@ def sim_fused(simlib, monkeypatch):
     """The network's layers go through encoders._fused and encoders.e4e, which ask their own lib() / stream()."""
     import hairfastgan_amd.encoders  # noqa: F401
 
-    for name in ("hairfastgan_amd.encoders._fused", "hairfastgan_amd.encoders.e4e"):
-        mod = sys.modules[name]
-        monkeypatch.setattr(mod, "lib", lambda: simlib)
-        monkeypatch.setattr(mod, "stream", lambda: None)
-        monkeypatch.setattr(mod, "require_gpu", lambda *a: None)
+    patch_host_modules(monkeypatch, simlib, ["hairfastgan_amd.encoders._fused", "hairfastgan_amd.encoders.e4e"])
     prev = simlib.hf_set_batch_invariant(1)  # the product's default (_runtime.lib() hands it to the library)
     yield simlib
     simlib.hf_set_batch_invariant(prev)

@@ -1,12 +1,12 @@
 """hipsim tests of the LPIPS and L2 / PSNR kernels (csrc/lpips.h) and their host mirror (hairfastgan_amd.lpips): the product's
 kernel sources interpreted on the CPU against the torch / numpy restatements (tests/lpips_ref.py) by the checks of
 tests/lpips_checks.py."""
-import sys
 
 import pytest
 import torch
 
 from tests import lpips_checks as K
+from tests.metric_common import patch_host_modules
 
 CPU = torch.device("cpu")
 
@@ -16,10 +16,7 @@ def sim_fused(simlib, monkeypatch):
     """The towers' 3x3 and 5x5 layers go through encoders._fused, which asks its own lib() / stream()."""
     import hairfastgan_amd.encoders  # noqa: F401
 
-    mod = sys.modules["hairfastgan_amd.encoders._fused"]
-    monkeypatch.setattr(mod, "lib", lambda: simlib)
-    monkeypatch.setattr(mod, "stream", lambda: None)
-    monkeypatch.setattr(mod, "require_gpu", lambda *a: None)
+    patch_host_modules(monkeypatch, simlib, ["hairfastgan_amd.encoders._fused"])
     return simlib
 
 

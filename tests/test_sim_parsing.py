@@ -1,6 +1,5 @@
 """CPU tests (kernel sources interpreted by tests/hipsim) of the face-parsing path:
 the oracle against the reference's golden masks, and the HIP-path BiSeNet mirror against the oracle on a small image."""
-import sys
 
 import numpy as np
 import pytest
@@ -10,6 +9,7 @@ import torch.nn.functional as F
 from hairfastgan_amd import _marshal as M
 from oracle import cases as C
 from oracle import ref_bisenet as BS
+from tests.metric_common import patch_host_modules
 
 
 def test_oracle_reproduces_reference_masks(golden):
@@ -32,11 +32,7 @@ def sim_parsing(simlib, monkeypatch):
     import hairfastgan_amd.encoders  # noqa: F401
     import hairfastgan_amd.face_parsing  # noqa: F401
 
-    for n in ("hairfastgan_amd.encoders._fused", "hairfastgan_amd.face_parsing"):
-        mod = sys.modules[n]
-        monkeypatch.setattr(mod, "lib", lambda: simlib)
-        monkeypatch.setattr(mod, "stream", lambda: None)
-        monkeypatch.setattr(mod, "require_gpu", lambda *a: None)
+    patch_host_modules(monkeypatch, simlib, ["hairfastgan_amd.encoders._fused", "hairfastgan_amd.face_parsing"])
     return simlib
 
 
@@ -124,8 +120,6 @@ def test_shape_adaptor_blocks_and_layout(simlib, monkeypatch, golden):
     label map of one pair bit for bit; (2) the HIP-backed mirror has the reference's state-dict layout; (3) its two
     non-standard blocks on the interpreted kernels - the 4x4 / stride-2 / pad-1 conv as a 3x3 conv of the space-to-depth
     input, and the per-sample LayerNorm (unbiased std, eps added to it) + LeakyReLU - against torch."""
-    import sys
-
     from hairfastgan_amd import shape_adaptor as SAP
     from oracle import ref_shape_adaptor as SA
 
@@ -141,10 +135,7 @@ def test_shape_adaptor_blocks_and_layout(simlib, monkeypatch, golden):
     assert {k: tuple(v.shape) for k, v in sd.items()} == SA.param_shapes() and list(sd) == list(SA.param_shapes())
     assert torch.equal(gen.hair_encoder.input_embedding[0], SA.pos_embedding())
 
-    for mod in (sys.modules["hairfastgan_amd.shape_adaptor"], sys.modules["hairfastgan_amd.encoders._fused"]):
-        monkeypatch.setattr(mod, "lib", lambda: simlib)
-        monkeypatch.setattr(mod, "stream", lambda: None)
-        monkeypatch.setattr(mod, "require_gpu", lambda *a: None)
+    patch_host_modules(monkeypatch, simlib, ["hairfastgan_amd.shape_adaptor", "hairfastgan_amd.encoders._fused"])
     torch.manual_seed(4)
     blk = SAP.Conv2dBlock(5, 24, 4, 2, padding=1, norm="ln", activation="lrelu")
     x = torch.randn(2, 5, 12, 20)

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from tests import png_decode_checks as K
+from tests.metric_common import patch_host_modules
 
 CPU = torch.device("cpu")
 
@@ -85,9 +86,7 @@ def test_malformed_stream(simlib, name, monkeypatch):
 
     K.check_malformed(simlib, None, CPU, name)
     data, stream_of, code = K.malformed_cases()[name]
-    monkeypatch.setattr(IU, "lib", lambda: simlib)
-    monkeypatch.setattr(IU, "stream", lambda: None)
-    monkeypatch.setattr(IU, "require_gpu", lambda *a: None)
+    patch_host_modules(monkeypatch, simlib, ["hairfastgan_amd.image_utils"])
     good = K.pil_file(K.picture((5, 9), 1), 0)
     bad = K.png_file(5, 9, 0, bytes(stream_of(K.idat_stream(data))))
     assert torch.equal(IU.decode_png(good, device="cpu"), torch.from_numpy(K.reference(good).copy()))

@@ -1,7 +1,6 @@
 """CPU tests of the SEAN inpainting stage: the oracle against the golden vectors the real
 reference produced, the product's state-dict layout, and - kernel sources interpreted by tests/hipsim - the whole
 HIP-path mirror (Zencoder, table-lookup convolutions, ACE tail, SPADE blocks) on a scaled-down model against the oracle."""
-import sys
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ from oracle import cases as C
 from oracle import ref_sean as SN
 from oracle import synth
 from tests import sean_checks as K
+from tests.metric_common import patch_host_modules
 
 CPU = torch.device("cpu")
 
@@ -134,11 +134,7 @@ def sim_sean(simlib, monkeypatch):
     import hairfastgan_amd.encoders  # noqa: F401
     import hairfastgan_amd.sean  # noqa: F401
 
-    for n in ("hairfastgan_amd.encoders._fused", "hairfastgan_amd.sean"):
-        mod = sys.modules[n]
-        monkeypatch.setattr(mod, "lib", lambda: simlib)
-        monkeypatch.setattr(mod, "stream", lambda: None)
-        monkeypatch.setattr(mod, "require_gpu", lambda *a: None)
+    patch_host_modules(monkeypatch, simlib, ["hairfastgan_amd.encoders._fused", "hairfastgan_amd.sean"])
     return simlib
 
 

@@ -22,24 +22,10 @@ sys.path.insert(0, ROOT)
 import PIL.Image  # noqa: E402
 import torch  # noqa: E402
 
+import bench_common as BC  # noqa: E402
 from hairfastgan_amd import _runtime  # noqa: E402
 from hairfastgan_amd import face_align as FA  # noqa: E402
 from tests import align_ref as R  # noqa: E402
-
-
-def device_ms(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1))
-    return {"median_ms": statistics.median(times), "min_ms": min(times), "max_ms": max(times), "iters": iters}
 
 
 def main():
@@ -61,8 +47,8 @@ def main():
         entry = {"image": [case[0], case[1]], "shrink": plan["shrink"], "crop": plan["crop"], "pad": plan["pad"],
                  "transform_input": list(plan["size"])}
         for key, fused in (("fused", True), ("chained", False)):
-            entry[f"align_face_{key}"] = device_ms(lambda: FA.align_face([img], [lm], fused=fused), args.warmup, args.iters)
-            entry[f"transform_resize_{key}"] = device_ms(
+            entry[f"align_face_{key}"] = BC.device_ms(lambda: FA.align_face([img], [lm], fused=fused), args.warmup, args.iters)
+            entry[f"transform_resize_{key}"] = BC.device_ms(
                 lambda: FA.transform_resize(L, st, padded, plan["quad"], 4096, 1024, fused=fused), args.warmup, args.iters)
         pil = PIL.Image.fromarray(arr, "RGB")
         cpu = []

@@ -23,6 +23,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
+import bench_common as BC  # noqa: E402
 from hairfastgan_amd import metrics as MT  # noqa: E402
 
 D, N, BATCH = 512, 2000, 128
@@ -105,10 +106,7 @@ def main():
                       "copied to the CPU and torchmetrics' formula with torch.linalg.eigvals (fp64) there; all by the host clock, "
                       "synchronised")
     print(json.dumps(result))
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(result, f)
-        f.write("\n")
+    BC.write_json(args.out, result)
     print("wrote", args.out)
 
 

@@ -12,7 +12,6 @@ their values).  Ratios are reported as measured, below 1 included.
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,24 +21,13 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 from torch import nn  # noqa: E402
 
+import bench_common as BC  # noqa: E402
 from hairfastgan_amd import _marshal as M  # noqa: E402
 from hairfastgan_amd import _runtime  # noqa: E402
 from hairfastgan_amd import identity as ID  # noqa: E402
 from hairfastgan_amd.encoders import _fused as FU  # noqa: E402
 
 BATCHES = (1, 8, 32)
-
-
-def seeded_state(model, seed=0):
-    """torch's default init with BatchNorm statistics away from (0, 1)."""
-    g = torch.Generator().manual_seed(seed)
-    sd = dict(model.state_dict())
-    for k, v in sd.items():
-        if k.endswith("running_var"):
-            sd[k] = 0.5 + torch.rand(v.shape, generator=g)
-        elif k.endswith("running_mean"):
-            sd[k] = 0.02 * torch.randn(v.shape, generator=g)
-    return sd
 
 
 def eager_unit(u, x):
@@ -59,32 +47,6 @@ def eager_feats(idl, x):
         x = eager_unit(u, x)
     x = net.output_layer(x)
     return x / torch.norm(x, 2, 1, True)
-
-
-def window_ms(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
-def compare(fns, iters, rounds):
-    """fns: {name: callable}; the routes alternate inside every round -> {name_ms: median, name_min_max_ms: [...]}"""
-    for fn in fns.values():
-        fn()  # warm-up of every shape
-    torch.cuda.synchronize()
-    times = {k: [] for k in fns}
-    for _ in range(rounds):
-        for k, fn in fns.items():
-            times[k].append(window_ms(fn, iters))
-    out = {}
-    for k, t in times.items():
-        out[f"{k}_ms"] = statistics.median(t)
-        out[f"{k}_min_max_ms"] = [min(t), max(t)]
-    return out
 
 
 def record_routes(idl, x):
@@ -117,21 +79,20 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "identity_bench.json"))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_identity.py measures on the GPU; none found")
+    BC.require_gpu("bench_identity.py")
     dev = torch.device("cuda:0")
     L, st = _runtime.lib(), _runtime.stream()
     result = {"metric": "identity", "device": torch.cuda.get_device_name(0), "iters": args.iters, "rounds": args.rounds,
               "conv_precision": _runtime.conv_precision(), "extract_feats": {}, "head": {}}
     g = torch.Generator().manual_seed(5)
     net = ID.Backbone(112, 50, "ir_se", drop_ratio=0.6)
-    net.load_state_dict(seeded_state(net))
+    net.load_state_dict(BC.seeded_bn_state(net))
     idl = ID.IDLoss(net.to(dev))
     with torch.inference_mode():
         result["routes_batch1"] = record_routes(idl, (torch.rand(1, 3, 256, 256, generator=g) * 2 - 1).to(dev))
         for batch in BATCHES:
             x = (torch.rand(batch, 3, 256, 256, generator=g) * 2 - 1).to(dev)
-            entry = compare({"device": lambda: idl.extract_feats(x), "eager": lambda: eager_feats(idl, x)}, args.iters, args.rounds)
+            entry = BC.compare({"device": lambda: idl.extract_feats(x), "eager": lambda: eager_feats(idl, x)}, args.iters, args.rounds)
             entry["eager_over_device"] = round(entry["eager_ms"] / entry["device_ms"], 3)
             entry["max_component_difference"] = float((idl.extract_feats(x) - eager_feats(idl, x)).abs().max())
             result["extract_feats"][f"b{batch}"] = entry
@@ -145,7 +106,7 @@ def main():
             fns = {"conv_route": lambda: FU.conv(feats.reshape(batch, -1, 1, 1), plan["head"], 1, 1, bias=plan["head_bias"]),
                    "linear_route": lambda: M.linear(L, st, flat, w_lin, b_lin),
                    "eager": lambda: net.output_layer(feats)}
-            entry = compare(fns, args.iters, args.rounds)
+            entry = BC.compare(fns, args.iters, args.rounds)
             a, b, c = (fn().reshape(batch, -1) for fn in fns.values())
             entry["conv_minus_eager"], entry["linear_minus_eager"] = float((a - c).abs().max()), float((b - c).abs().max())
             entry["conv_route_kernel"] = FU.conv_route(plan["head"], 1, 1, 1, 1, {"bias": plan["head_bias"]}, batch=batch)
@@ -156,10 +117,7 @@ def main():
                       "the folded Linear as a 1x1 conv through the route table (what the product runs), as hf_linear_f32, and the "
                       "three eager layers; device events around back-to-back calls, the routes alternating, medians of the windows")
     print(json.dumps(result))
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(result, f)
-        f.write("\n")
+    BC.write_json(args.out, result)
     print("wrote", args.out)
 
 

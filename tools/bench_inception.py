@@ -11,7 +11,6 @@ reported as measured, below 1 included.
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -21,23 +20,12 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
+import bench_common as BC  # noqa: E402
 from hairfastgan_amd import _runtime  # noqa: E402
 from hairfastgan_amd.inception import InceptionV3  # noqa: E402
 from hairfastgan_amd.metrics import FrechetDistance  # noqa: E402
 
 BATCHES = {1: 10, 32: 3, 128: 2}  # batch -> calls per window
-
-
-def seeded_state(model, seed=0):
-    """torch's default init with BatchNorm statistics away from (0, 1)."""
-    g = torch.Generator().manual_seed(seed)
-    sd = dict(model.state_dict())
-    for k, v in sd.items():
-        if k.endswith("running_var"):
-            sd[k] = 0.5 + torch.rand(v.shape, generator=g)
-        elif k.endswith("running_mean"):
-            sd[k] = 0.02 * torch.randn(v.shape, generator=g)
-    return sd
 
 
 def eager_bc(m, x):
@@ -81,58 +69,25 @@ def eager_features(net, images):
     return x.mean((2, 3))
 
 
-def window_ms(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
-def compare(fns, iters, rounds):
-    """fns: {name: callable}; the routes alternate inside every round -> {name_ms: median, name_min_max_ms: [...]}"""
-    for fn in fns.values():
-        fn()  # warm-up of every shape
-    torch.cuda.synchronize()
-    times = {k: [] for k in fns}
-    for _ in range(rounds):
-        for k, fn in fns.items():
-            times[k].append(window_ms(fn, iters))
-    out = {}
-    for k, t in times.items():
-        out[f"{k}_ms"] = statistics.median(t)
-        out[f"{k}_min_max_ms"] = [min(t), max(t)]
-    return out
-
-
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--no_frechet", action="store_true", help="skip the d = 2048 FrechetDistance.compute() timing")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "inception_bench.json"))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_inception.py measures on the GPU; none found")
+    BC.require_gpu("bench_inception.py")
     dev = torch.device("cuda:0")
     result = {"metric": "inception_fid", "device": torch.cuda.get_device_name(0), "rounds": args.rounds,
               "conv_precision": _runtime.conv_precision(), "features_2048": {}}
     g = torch.Generator().manual_seed(5)
     net = InceptionV3(2048)
-    net.load_state_dict(seeded_state(net))
+    net.load_state_dict(BC.seeded_bn_state(net))
     net = net.to(dev)
-
-    def save():
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(result, f)
-            f.write("\n")
 
     with torch.inference_mode():
         for batch, iters in BATCHES.items():
             x = torch.randint(0, 256, (batch, 3, 299, 299), generator=g).to(torch.uint8).to(dev)
-            entry = compare({"device": lambda: net(x), "eager": lambda: eager_features(net, x)}, iters, args.rounds)
+            entry = BC.compare({"device": lambda: net(x), "eager": lambda: eager_features(net, x)}, iters, args.rounds)
             entry["iters"] = iters
             entry["eager_over_device"] = round(entry["eager_ms"] / entry["device_ms"], 3)
             entry["images_per_s_device"] = round(1000.0 * batch / entry["device_ms"], 1)
@@ -140,7 +95,7 @@ def main():
             result["features_2048"][f"b{batch}"] = entry
             result["launches_per_forward"] = net.launches
             print("features_2048", batch, json.dumps(entry), flush=True)
-            save()
+            BC.write_json(args.out, result)
         if not args.no_frechet:
             fid = FrechetDistance(lambda f: f)
             fid.update_features((torch.randn(2000, 2048, generator=g) * 0.3 + 0.5).to(dev), True)
@@ -159,7 +114,7 @@ def main():
                       "the windows; frechet: one FrechetDistance.compute() (two Jacobi eigensolves) timed on the host around a "
                       "device synchronisation")
     print(json.dumps(result))
-    save()
+    BC.write_json(args.out, result)
     print("wrote", args.out)
 
 

@@ -24,26 +24,12 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+import bench_common as BC  # noqa: E402
 from hairfastgan_amd import _marshal as M  # noqa: E402
 from hairfastgan_amd._runtime import lib, stream  # noqa: E402
 from tests import png_checks as K  # noqa: E402
 
 SETTINGS = [(75, "4:2:0"), (95, "4:4:4")]
-
-
-def _time(fn, reps):
-    """median milliseconds of `fn` between device events (after three warm-up calls)"""
-    for _ in range(3):
-        fn()
-    times = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1))
-    return float(np.median(times))
 
 
 def _wall(fn, reps):
@@ -104,7 +90,7 @@ def main():
                 n = sizes.cpu().tolist()
                 for k in {0, batch - 1}:
                     assert files[k, :n[k]].cpu().numpy().tobytes() == pil_file, (name, quality, subsampling, batch, k)
-                ms = _time(lambda: M.jpeg_encode(L, st, x, quality, sub), a.reps)
+                ms = BC.time_ms(lambda: M.jpeg_encode(L, st, x, quality, sub), a.reps)
                 wall = _wall(lambda: M.jpeg_encode(L, st, x, quality, sub), a.reps)
                 setting[f"batch_{batch}"] = {"device_ms": round(ms, 4), "device_ms_per_image": round(ms / batch, 4),
                                              "host_clock_ms_per_call": round(wall, 4),

@@ -12,7 +12,6 @@ sample) over its time.
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,6 +20,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
+import bench_common as BC  # noqa: E402
 from hairfastgan_amd import _marshal as M  # noqa: E402
 from hairfastgan_amd import _runtime  # noqa: E402
 from hairfastgan_amd import lpips as LP  # noqa: E402
@@ -69,26 +69,11 @@ def eager_layer(fx, fy, w):
     return F.conv2d((nx - ny) ** 2, w.reshape(1, -1, 1, 1)).mean((2, 3)).reshape(-1)
 
 
-def window_ms(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
 def compare(device_fn, eager_fn, iters, rounds):
-    device_fn(), eager_fn()  # warm-up of every shape
-    torch.cuda.synchronize()
-    dev, ref = [], []
-    for _ in range(rounds):
-        dev.append(window_ms(device_fn, iters))
-        ref.append(window_ms(eager_fn, iters))
-    d, r = statistics.median(dev), statistics.median(ref)
-    return {"device_ms": d, "eager_ms": r, "eager_over_device": round(r / d, 3), "device_min_max_ms": [min(dev), max(dev)],
-            "eager_min_max_ms": [min(ref), max(ref)]}
+    """bench_common.compare of the two routes, with their ratio, in this file's key order."""
+    t = BC.compare({"device": device_fn, "eager": eager_fn}, iters, rounds)
+    return {"device_ms": t["device_ms"], "eager_ms": t["eager_ms"], "eager_over_device": round(t["eager_ms"] / t["device_ms"], 3),
+            "device_min_max_ms": t["device_min_max_ms"], "eager_min_max_ms": t["eager_min_max_ms"]}
 
 
 def main():
@@ -97,8 +82,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lpips_bench.json"))
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_lpips.py measures on the GPU; none found")
+    BC.require_gpu("bench_lpips.py")
     dev = torch.device("cuda:0")
     L, st = _runtime.lib(), _runtime.stream()
     result = {"metric": "lpips", "device": torch.cuda.get_device_name(0), "iters": args.iters, "rounds": args.rounds,
@@ -141,10 +125,7 @@ def main():
                       "reference's route in eager torch on the same GPU and parameters; device events around back-to-back calls, "
                       "the routes alternating, medians of the windows")
     print(json.dumps(result))
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(result, f)
-        f.write("\n")
+    BC.write_json(args.out, result)
     print("wrote", args.out)
 
 

@@ -27,6 +27,7 @@ import numpy as np  # noqa: E402
 import PIL.Image  # noqa: E402
 import torch  # noqa: E402
 
+import bench_common as BC  # noqa: E402
 from hairfastgan_amd import _marshal as M  # noqa: E402
 from hairfastgan_amd import _runtime  # noqa: E402
 from hairfastgan_amd import face_align as FA  # noqa: E402
@@ -40,21 +41,6 @@ CASES = {
     "up": (2400, 2000, 12, (1200, 920, 400, 7.0)),
     "photo_12mp": (4000, 3000, 13, (2000, 1400, 700, -4.0)),
 }
-
-
-def device_ms(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1))
-    return {"median_ms": statistics.median(times), "min_ms": min(times), "max_ms": max(times), "iters": iters}
 
 
 def main():
@@ -80,10 +66,10 @@ def main():
         coef = FA.quad_coefficients(inv["quad"], x1 - x0, y1 - y0)
         entry = {"photo": [w, h], "shrink": stages["plan"]["shrink"], "n": inv["n"], "roi": list(inv["roi"]),
                  "roi_pixels": (x1 - x0) * (y1 - y0)}
-        entry["paste_back"] = device_ms(lambda: FA.paste_back(img, F_float, lm, output_size=S), args.warmup, args.iters)
+        entry["paste_back"] = BC.device_ms(lambda: FA.paste_back(img, F_float, lm, output_size=S), args.warmup, args.iters)
         work = img.clone()  # (pasted over again at every run: the time does not depend on the bytes)
-        entry["paste_quad_launch"] = device_ms(lambda: M.paste_quad_u8(L, st, work, stages["result"], stages["mask"], coef, inv["roi"]),
-                                               args.warmup, args.iters)
+        entry["paste_quad_launch"] = BC.device_ms(lambda: M.paste_quad_u8(L, st, work, stages["result"], stages["mask"], coef, inv["roi"]),
+                                                  args.warmup, args.iters)
         photo, res = PIL.Image.fromarray(arr, "RGB"), PIL.Image.fromarray(F, "RGB")
         cpu = []
         for _ in range(args.cpu_repeats):

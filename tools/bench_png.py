@@ -25,25 +25,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+import bench_common as BC  # noqa: E402
 from hairfastgan_amd import _marshal as M  # noqa: E402
 from hairfastgan_amd import image_utils as IU  # noqa: E402
 from hairfastgan_amd._runtime import lib, stream  # noqa: E402
 from tests import png_checks as K  # noqa: E402
-
-
-def _time(fn, reps):
-    """median milliseconds of `fn` between device events (after three warm-up calls)"""
-    for _ in range(3):
-        fn()
-    times = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1))
-    return float(np.median(times))
 
 
 def _pil(img, level, reps):
@@ -95,9 +81,9 @@ def main():
             assert len(set(n)) == 1  # batch-invariant
             for k in {0, batch - 1}:
                 assert np.array_equal(K.decode_pil(files[k, :n[k]].cpu().numpy().tobytes())[0], host), (name, batch, k)
-            ms = _time(lambda: M.png_encode(L, st, x, 3), a.reps)
+            ms = BC.time_ms(lambda: M.png_encode(L, st, x, 3), a.reps)
             dst = torch.empty_like(x)
-            copy_ms = _time(lambda: dst.copy_(x), a.reps)
+            copy_ms = BC.time_ms(lambda: dst.copy_(x), a.reps)
             entry[f"batch_{batch}"] = {"device_ms": round(ms, 4), "device_ms_per_image": round(ms / batch, 4),
                                        "device_copy_ms": round(copy_ms, 4), "times_the_copy": round(ms / copy_ms, 1),
                                        "file_bytes": n[0],
