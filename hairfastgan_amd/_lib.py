@@ -16,6 +16,7 @@ _f = ctypes.c_void_p      # float* / const float* (device pointers)
 _i = ctypes.c_int
 _ll = ctypes.c_longlong
 _fl = ctypes.c_float
+_d = ctypes.c_double
 _st = ctypes.c_void_p     # hipStream_t
 
 # name -> argtypes of a function that returns int (0 == HF_OK), or (restype, argtypes).
@@ -96,6 +97,9 @@ SIGNATURES = {
     "hf_lpips_layer_work_doubles": (_ll, [_i, _i, _i]),
     "hf_sq_err_sum_f64": [_f, _f, _f, _f, _i, _ll, _i, _st],
     "hf_sq_err_sum_work_doubles": (_ll, [_i, _ll]),
+    "hf_ssim_planes_f64": [_f, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _d, _d, _d, _st],
+    "hf_ssim_work_doubles": (_ll, [_i, _i, _i, _i]),
+    "hf_ssim_tile": [_i],
     "hf_crop_avgpool_f32": [_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _st],
     "hf_l2_normalize_rows_f32": [_f, _f, _f, _i, _i, _st],
     "hf_row_similarity_f64": [_f, _f, _f, _i, _i, _i, _i, _st],

@@ -1746,6 +1746,48 @@ def sq_err_sum(lib, st, a, b):
     return out
 
 
+SSIM_DTYPES = {torch.uint8: 0, torch.float32: 1, torch.float64: 2}
+
+
+def ssim_planes(lib, st, x, y, taps, c1, c2, cn, mask=None, want_cs=False, want_map=False, want_next=False):
+    """hf_ssim_planes_f64 (csrc/ssim.h) of images x, y [N,C,H,W], both uint8, fp32 or fp64; taps: the 1-D window, float64 on the
+    device.  -> {"s": [N,C] float64 sums of S over the valid region} plus, on request, "cs" (sums of cs), "map" [N,C,oh,ow],
+    "next" (the 2x2 means of x and of y, float64 [N,C,H//2,W//2]).  mask: fp32 [N,oh,ow] weights shared by an image's
+    channels; then "s" holds the sums of m S and "m" those of m (want_cs is not available with a mask)."""
+    if x.shape != y.shape or x.dtype != y.dtype or x.dtype not in SSIM_DTYPES or x.ndim != 4:
+        raise ValueError(f"two uint8, fp32 or fp64 images [N,C,H,W] of one shape; got {x.dtype} {tuple(x.shape)}, {y.dtype} {tuple(y.shape)}")
+    if mask is not None and want_cs:
+        raise ValueError("the second sum is the mask's with a mask: no cs sums")
+    x, y = x.contiguous(), y.contiguous()
+    n, c, h, w = x.shape
+    win = taps.numel()
+    _f64(taps, (win,), "taps")
+    oh, ow = h - win + 1, w - win + 1
+    if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != (n, oh, ow) or not mask.is_contiguous() or
+                             mask.device != x.device):
+        raise ValueError(f"mask must be a contiguous fp32 tensor of shape {(n, oh, ow)} on {x.device}; got {mask.dtype} "
+                         f"{tuple(mask.shape)} on {mask.device}")
+    if y.device != x.device or taps.device != x.device:
+        raise ValueError(f"x, y and taps must share a device; got {x.device}, {y.device}, {taps.device}")
+
+    def f64(*shape):
+        return torch.empty(shape, dtype=torch.float64, device=x.device)
+
+    out = {"s": f64(n, c)}
+    aux = f64(n, c) if want_cs or mask is not None else None
+    if aux is not None:
+        out["m" if mask is not None else "cs"] = aux
+    if want_map:
+        out["map"] = f64(n, c, max(oh, 0), max(ow, 0))
+    if want_next:
+        out["next"] = (f64(n, c, h // 2, w // 2), f64(n, c, h // 2, w // 2))
+    nx, ny = out.get("next", (None, None))
+    work = f64(max(int(lib.hf_ssim_work_doubles(n * c, h, w, win)), 1))
+    check(lib, lib.hf_ssim_planes_f64(_p(out["s"]), _p(aux), _p(out.get("map")), _p(nx), _p(ny), _p(x), _p(y), _p(mask), _p(taps), _p(work),
+                                      SSIM_DTYPES[x.dtype], n * c, c, h, w, win, float(c1), float(c2), float(cn), st), "hf_ssim_planes_f64")
+    return out
+
+
 # ---- identity similarity (csrc/identity.h; hairfastgan_amd.identity chains these) ----
 def crop_avgpool(lib, st, x, y0, x0, ch, cw, oh, ow, scale=None, shift=None):
     """hf_crop_avgpool_f32: AdaptiveAvgPool2d((oh, ow)) of x[:, :, y0:y0+ch, x0:x0+cw], the window read in place;

@@ -10,7 +10,7 @@ OBJS=""
 PIDS=""
 for f in api elementwise upfirdn2d style torgb modconv convh convh_enc encoder_ops sean vit gemm_h stem convrow; do
   DEPS="$f.hip hf_common.h conv_common.h ../../include/hairfast_hip.h"
-  [ $f = encoder_ops ] && DEPS="$DEPS poisson.h align.h paste.h export.h codec_common.h png.h jpeg.h jpeg_decode.h png_decode.h metric_common.h frechet.h lpips.h identity.h inception.h"  # what it includes
+  [ $f = encoder_ops ] && DEPS="$DEPS poisson.h align.h paste.h export.h codec_common.h png.h jpeg.h jpeg_decode.h png_decode.h metric_common.h frechet.h lpips.h ssim.h identity.h inception.h"  # what it includes
   [ $f = gemm_h ] && DEPS="$DEPS conv_rect.h"
   STALE=""
   for d in $DEPS; do

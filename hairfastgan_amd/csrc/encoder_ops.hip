@@ -32,6 +32,7 @@
 #include "png_decode.h"
 #include "frechet.h"
 #include "lpips.h"
+#include "ssim.h"
 #include "identity.h"
 #include "inception.h"
 

@@ -2,8 +2,8 @@
 models/encoder4editing/criteria/lpips, models/FeatureStyleEncoder/lpips, losses/lpips; the scoring command line
 models/encoder4editing/scripts/calc_losses_on_images.py).
 
-    python -m hairfastgan_amd.lpips --data_path DIR --gt_path DIR [--mode lpips|l2|psnr] [--net alex|vgg] [--size 256]
-                                    [--image_decoder pil|device] [--batch 4]
+    python -m hairfastgan_amd.lpips --data_path DIR --gt_path DIR [--mode lpips|l2|psnr|ssim|ms_ssim] [--net alex|vgg]
+                                    [--ssim_window gaussian|uniform] [--size 256] [--image_decoder pil|device] [--batch 4]
 
 Pieces, all on the library's kernels:
   images -> features      the AlexNet / VGG16 `features` towers (published layer tables): the first layer with the z-score as
@@ -11,6 +11,7 @@ Pieces, all on the library's kernels:
                           matrix-core routes), AlexNet's 5x5 layer as a GEMM over unfolded patches, hf_maxpool2d_f32 between
   features -> distance    hf_lpips_layer_f64 per tap: normalise, subtract, square, weigh and average in one launch
   L2 / PSNR               hf_sq_err_sum_f64
+  SSIM / MS-SSIM          `hairfastgan_amd.ssim` (hf_ssim_planes_f64); here only the command line's two modes
 The SqueezeNet tower, the masked and the scale-weighted variants and everything with gradients are not part of this backend.
 
 `lib=None`: the loaded HIP library on torch's current stream.  Tests hand in the CPU interpreter build of the same kernel
@@ -165,9 +166,10 @@ def main(argv=None, model=None, lib=None, device=None):
     --gt_path and writes inference_metrics/scores_<mode>.json and stat_<mode>.txt next to --data_path (`metrics.score_pairs`).
     `model`: the LPIPS module (default: LPIPS(--net) with the weights `checkpoints.lpips_weights` finds).
     -> {file name: score}."""
-    parser = argparse.ArgumentParser(prog="python -m hairfastgan_amd.lpips", description="LPIPS / L2 / PSNR of a folder of results")
-    parser.add_argument("--mode", choices=("lpips", "l2", "psnr"), default="lpips")
+    parser = argparse.ArgumentParser(prog="python -m hairfastgan_amd.lpips", description="LPIPS / L2 / PSNR / SSIM / MS-SSIM of a folder of results")
+    parser.add_argument("--mode", choices=("lpips", "l2", "psnr", "ssim", "ms_ssim"), default="lpips")
     parser.add_argument("--net", choices=("alex", "vgg"), default="alex")
+    parser.add_argument("--ssim_window", choices=("gaussian", "uniform"), default="gaussian", help="the window of --mode ssim / ms_ssim")
     add_pair_arguments(parser, batch=4)
     args = parser.parse_args(argv)
 
@@ -177,6 +179,10 @@ def main(argv=None, model=None, lib=None, device=None):
             return psnr(res, gt, lib=lib)
         if args.mode == "l2":
             return mse(unit_range(res), unit_range(gt), lib)
+        if args.mode in ("ssim", "ms_ssim"):  # on the bytes themselves (data range 255)
+            from . import ssim as SS
+
+            return getattr(SS, args.mode)(res, gt, window=args.ssim_window, lib=lib)
         if model is None:
             from .checkpoints import lpips_weights
 
@@ -185,7 +191,9 @@ def main(argv=None, model=None, lib=None, device=None):
             model = model.to(device if device is not None else "cuda")
         return model.per_sample(unit_range(res), unit_range(gt))
 
-    return score_pairs(args, score, args.mode, "Average loss is {:.2f}+-{:.2f}", device, lib)
+    # SSIM differences live in the third decimal
+    sentence = f"Average {args.mode} is {{:.4f}}+-{{:.4f}}" if args.mode in ("ssim", "ms_ssim") else "Average loss is {:.2f}+-{:.2f}"
+    return score_pairs(args, score, args.mode, sentence, device, lib)
 
 
 if __name__ == "__main__":

@@ -895,6 +895,36 @@ int hf_sq_err_sum_f64(double *out, const void *a, const void *b, double *work, i
 long long hf_sq_err_sum_work_doubles(int n, long long per_image);
 
 /* ---------------------------------------------------------------------------
+ * Structural similarity (csrc/ssim.h; losses/lpips/__init__.py:52-53 `dssim`, networks_basic.py:167 `DSSIM`, there a call
+ * into scikit-image on the host).  One fused launch plus the fixed-order finish; everything is fp64 without contraction;
+ * no atomics, one owner per output element: a plane's bits depend on the plane alone.
+ *
+ * hf_ssim_planes_f64: x, y are `planes` planes [h,w] of dtype 0 (uint8), 1 (fp32) or 2 (fp64).  taps[0..win) fp64 (device
+ * memory), win odd in 3..11, is applied separably as a correlation over the valid region only,
+ *   f(z)[i,j] = sum_a taps[a] (sum_b taps[b] z[i+a, j+b]),  a and b ascending,  i < oh = h-win+1, j < ow = w-win+1.
+ * Per output pixel, in exactly this order of operations:
+ *   ux, uy, uxx, uyy, uxy = f(x), f(y), f(x x), f(y y), f(x y)
+ *   vx = cn (uxx - ux ux), vy = cn (uyy - uy uy), vxy = cn (uxy - ux uy)
+ *   cs = (2 vxy + c2) / (vx + vy + c2)
+ *   S  = ((2 ux uy + c1) (2 vxy + c2)) / ((ux ux + uy uy + c1) (vx + vy + c2))
+ * so that S(x, x) = 1 and S(x, y) = S(y, x) hold bit for bit.  Outputs (NULL = not wanted, except sum_s):
+ *   sum_s [planes]       sum of S over the plane's valid region; with a mask: sum of m S
+ *   sum_aux [planes]     sum of cs; with a mask: sum of m
+ *   map [planes,oh,ow]   S itself
+ *   next_x, next_y [planes, h/2, w/2] (floored; both or neither)  the 2x2 means (((a00 + a01) + a10) + a11) / 4 of x and
+ *                        of y in fp64, a trailing odd row or column dropped: the next pyramid level of MS-SSIM
+ * mask: fp32 weights [planes / channels, oh, ow], one map shared by the `channels` planes of an image (channels is only read
+ * with a mask).  Block partials go to work (hf_ssim_work_doubles(planes, h, w, win) doubles) and are added in a fixed order.
+ * HF_E_INVALID: a NULL (sum_s, x, y, taps, work) or misaligned pointer, an unknown dtype, win even or outside 3..11, h < win
+ * or w < win, planes <= 0 or > 65535, only one of next_x / next_y, a next level with h < 2 or w < 2, a mask with channels <= 0
+ * or planes % channels != 0.  hf_ssim_tile(0 / 1): the rows / columns of a block's output tile (for tests). */
+int hf_ssim_planes_f64(double *sum_s, double *sum_aux, double *map, double *next_x, double *next_y, const void *x, const void *y,
+                       const float *mask, const double *taps, double *work, int dtype, int planes, int channels, int h, int w,
+                       int win, double c1, double c2, double cn, void *stream);
+long long hf_ssim_work_doubles(int planes, int h, int w, int win);
+int hf_ssim_tile(int axis);
+
+/* ---------------------------------------------------------------------------
  * Identity similarity (csrc/identity.h; ArcFace IR-SE50 `IDLoss`, losses/pp_losses.py:267-296 and
  * models/encoder4editing/criteria/id_loss.py): what stands around the network's body.  One owner per output element, every
  * sum in a fixed order: an image's, a row's or an entry's bits do not depend on what else the launch holds.
